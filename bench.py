@@ -11,9 +11,16 @@ positions over the model's 588 (ViT, T5 encoder, T5 decoder alike); the closing 
 the score reduction and the allocator are inside the timed region.
 
     python bench.py --gpus 1 --steps 12 --warmup 2
+    python bench.py --gpus 1 --steps 12 --warmup 2 --full  (+ the legs outside the headline)
+    python bench.py --gpus 1 --steps 12 --warmup 2 --dump-outputs DIR
     python bench.py --gpus N --steps K --warmup W          (starts its own N ranks, see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the
+headline does not need, all outside the timed region: the z-mode parity leg, the K1 event-pair
+floor, the box's fill rate and the CPU baseline (`--no-parity-leg` / `--no-cpu-baseline` still
+drop one of them).  `--dump-outputs DIR` writes what the timed pass returned (see dump_outputs).
 
 `--gpus N` with N > 1 and no launcher environment (WORLD_SIZE unset): this process makes no
 GPU call at all; it starts N children of itself, one per GPU (RANK / LOCAL_RANK / WORLD_SIZE /
@@ -51,6 +58,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--num-data", type=int, default=128, help="calibration pairs per rank")
     ap.add_argument("--batch-size", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the z-mode parity leg, the K1 event-pair "
+                         "floor, the box's fill rate and the CPU baseline (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed pass returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--layers", default=None,
                     help="analysis only: comma-separated matrix indices to time instead of the strided "
@@ -109,7 +121,8 @@ def parse():
                          "who swaps the import hands the pruners (INTEGRATION.md §A) — scored through "
                          "pruners/hooked_prefix.py (no HIP graphs; the chunk's evaluations in lock step)")
     ap.add_argument("--no-parity-leg", action="store_true",
-                    help="skip the short leg after the timed region that scores two blocks in each z mode")
+                    help="with --full: skip the short leg after the timed region that scores two blocks "
+                         "in each z mode")
     ap.add_argument("--no-k1-events", action="store_true",
                     help="no event pairs, no blocker: the uninstrumented loop (rocprofv3 "
                          "cross-check of the K1 durations; the line then carries no roofline)")
@@ -134,6 +147,13 @@ def strided(n_total, k, offset=0, run=6, block_starts=None):
         for j in range(run):
             if len(out) < k:
                 out.append(min(n_total - 1, start + j))
+    if len(set(out)) < len(out):
+        # k above ~n_total / 2: runs overlap, and a matrix scored twice is one step.  Keep the
+        # first occurrences and take the lowest matrices not yet in the sample, so that the
+        # sample is k distinct matrices (the timed pass visits them in model order)
+        seen = list(dict.fromkeys(out))
+        rest = [i for i in range(n_total) if i not in set(seen)]
+        out = sorted(seen + rest[:k - len(seen)])
     return out
 
 
@@ -459,6 +479,10 @@ def main():
     params_by_name = dict(model.named_parameters())
     numel_total = sum(params_by_name[k].numel() for k in prunable)
     build_s = time.time() - t_build
+    if not args.layers and not 1 <= args.steps <= n_total:
+        print(f"bench.py: --steps {args.steps}: a step scores one of the model's {n_total} matrices",
+              file=sys.stderr)
+        sys.exit(2)
 
     kern = TimedKernels(hip.HipKernels())
     kern.blocker = {"spin": "spin", "none": None,
@@ -560,14 +584,16 @@ def main():
     class _Snap:
         stats = timed_stats or {}
     snap = _Snap() if timed_stats is not None else object()
-    # ---- outside the timed region: the three ways K1 can get its z, on the same matrices ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ls, table, [prunable[i] for i in layer_ids], params_by_name)
+    # ---- --full, outside the timed region: the three ways K1 can get its z, on the same matrices ----
     # One ViT-g block and one FlanT5 decoder block, each scored three times from the same cached
     # prefix: "torch" = the reference's draw regenerated in registers (the default, the timed
     # region's mode unless --z-source says otherwise), "torch_materialised" = every z drawn by
     # torch.normal itself and read from memory (round 4's default; what the start-up probe falls
     # back to), "philox" = the build's own in-register stream.
     z_modes = None
-    if not args.no_parity_leg and not args.full_forward and world == 1 and not emulated:
+    if args.full and not args.no_parity_leg and not args.full_forward and world == 1 and not emulated:
         kern.enabled = False
         vit_blocks = [b for b in block_starts if prunable[b].startswith("visual_encoder")]
         dec_blocks = [b for b in block_starts if ".decoder." in prunable[b]]
@@ -758,10 +784,11 @@ def main():
                        "(hipExtLaunchKernelGGL)" if kind in ("units", "block") else
                        f"torch event pair behind a '{args.k1_blocker}' blocker"),
             "per_launch": k1["per_launch"],
-            # not subtracted from anything: `achieved` is the raw reading
-            "event_pair_floor_us": kern.event_floor_us() if kind in ("units", "block") else None,
-            # context, not a peak: the same box's single-stream fill rate right after the run
-            "box_fill_gbs": kern.box_write_gbs(),
+            # --full only.  Not subtracted from anything: `achieved` is the raw reading
+            "event_pair_floor_us": (kern.event_floor_us() if args.full and kind in ("units", "block")
+                                    else None),
+            # --full only.  Context, not a peak: the same box's single-stream fill rate right after the run
+            "box_fill_gbs": kern.box_write_gbs() if args.full else None,
             "algorithmic_bytes_per_launch": k1["bytes_per_launch"],
             "bytes_rule": {
                 "units": "(2*U+2)*s*numel per launch: read W once, write theta+/theta- for each of "
@@ -787,7 +814,7 @@ def main():
         }
     if z_modes is not None:
         out["z_modes"] = z_modes
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, prunable, batches_local, args)
     if rank == 0:
         print(json.dumps(out))
@@ -801,6 +828,36 @@ def _pinned_gemm_report():
         return fused.gemm_report()
     except Exception as e:          # never let the report break the line
         return {"error": repr(e)}
+
+
+def dump_outputs(out_dir, ls, table, names, params_by_name, per_matrix=16384, budget=48 << 20):
+    """What the timed pass handed its caller, as DIR/<name>.npy, for comparing two builds output
+    for output (the inputs are seeded: the same arguments give the same model and batches).
+    The timed pass is one `return_sparsity()` over the K timed matrices; its result exists once the
+    last step is done.  Arrays follow the order of `names` (the timed matrices, model order):
+      sparsity.npy        float64 [K]     the returned {matrix: sparsity} table
+      importance.npy      float64 [K]     the matrices' importance scores the table was allocated from
+      loss_table.npy      float32 [U, 2]  the (theta+, theta-) loss of every (matrix, batch) unit
+      weights_sample.npy  float32 [K, S]  the matrices as the pass leaves them in the model (K1's
+                                          drift), S elements each at fixed seeded positions
+    Well under 64 MB for any K the bench accepts."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "sparsity": np.array([float(table[n]) for n in names], dtype=np.float64),
+        "importance": np.array([ls._layer_sum(n) for n in names], dtype=np.float64),
+    }
+    if getattr(ls, "loss_table", None) is not None:
+        arrays["loss_table"] = np.asarray(ls.loss_table, dtype=np.float32)
+    rng = np.random.default_rng(20240917)          # a local generator: the global RNGs stay put
+    s = max(1, min(per_matrix, budget // (4 * max(1, len(names)))))
+    rows = []
+    for n in names:
+        w = params_by_name[n].detach().reshape(-1)
+        idx = np.sort(rng.integers(0, w.numel(), size=s))
+        rows.append(w[torch.from_numpy(idx).to(w.device)].float().cpu().numpy())
+    arrays["weights_sample"] = np.stack(rows).astype(np.float32)
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
 
 
 def _blocked(loss_fn):

@@ -1,12 +1,12 @@
 #!/bin/bash
-# The bench four ways: the driver's command (default z = the reference's draw in registers), the
+# The bench four ways: the driver's command with --full (default z = the reference's draw in registers), the
 # model with its stage_plan() hidden (--unstaged), the build's own stream (--z-source philox), and
 # the driver's command under rocprofv3 --kernel-trace --stats (summaries for profiles/).
 #   gpurun --timeout 1800 -- 'bash tools/gpu_runs/bench.sh [tag]'
 cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=${1:-bench}; O=gpurun_out/$TAG; mkdir -p $O; export TMPDIR=/tmp
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --unstaged --no-cpu-baseline > $O/bench_unstaged.json 2> $O/bench_unstaged.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --unstaged --full --no-cpu-baseline > $O/bench_unstaged.json 2> $O/bench_unstaged.err
 timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --z-source philox --no-cpu-baseline --no-parity-leg > $O/bench_philox.json 2> $O/bench_philox.err
 bash tools/run_prof_bench.sh $TAG/prof 20 5 > $O/prof_bench.log 2>&1
 cd "$GRAFT_REPO_ROOT"
