@@ -344,7 +344,13 @@ __global__ __launch_bounds__(256) void chol_finalize_kernel(float* __restrict__ 
 //      per level, log2(n / 64) levels, every pair of a level in one launch;
 //   3. out = X^T X on the tiles i >= j (k from the later of the two block rows), mirrored.
 // Every product on v_mfma_f32_32x32x2_f32, 64 x 64 tiles, K in chunks of 64 through LDS, every
-// sum in a fixed order.
+// sum in a fixed order.  The MFMA accumulates like a k-ordered fmaf chain, so one accumulator over
+// the whole K range (up to n in step 3) rounds like a serial sum of n terms: the inverse drifted
+// from 1.9e-6 at n = 768 to 7.0e-6 of its scale at 6144 against fp64, 5-6x the library's
+// (profiles/r06_cholesky/own_cholesky_bench.txt), with X = inv(L) itself accurate to ~1e-7.  So
+// every 64-k chunk goes into a fresh partial and the partials are added with a two-sum into a
+// (sum, compensation) pair (tile_gemm): a chunk's own error is that of 64 terms, and the adds
+// across chunks lose next to nothing.  The order is fixed: bit-repeatable, and nothing is shared.
 template <int T, int S0>
 static __device__ __forceinline__ void fmac8_regs(float (&b)[CH_NB], const float (&a)[CH_NB], float m) {
     // b[S0 + k] += m * (a[S0 + k] of lane T), k = 0 .. 7
@@ -425,14 +431,20 @@ __global__ __launch_bounds__(64) void trinv_ragged_kernel(const float* __restric
         for (int c = 0; c < m; ++c) X[(k0 + i) * ldx + k0 + c] = c <= i ? b[c] : 0.0f;
 }
 
-// One 64 x 64 tile of C = alpha * op(A) B over k in [k_lo, k_hi): A [i][k] (TA: stored [k][i]),
+// One 64 x 64 tile of C = op(A) B over k in [k_lo, k_hi) into acc: A [i][k] (TA: stored [k][i]),
 // B stored [k][j].  Rows / columns / k past the given extents read as zeros.
+// Each 64-k chunk is a fresh partial; the partials are summed with Knuth's two-sum (exact error of
+// each add, whichever operand is larger) into (sum, comp), and acc = sum + comp.  The build has
+// -ffp-contract=off and no fast-math: the compiler neither fuses nor re-associates these adds.
 template <bool TA>
 static __device__ __forceinline__ void tile_gemm(const float* __restrict__ Ap, int64_t lda, int64_t a_rows,
                                                  const float* __restrict__ Bp, int64_t ldb, int64_t b_cols,
                                                  int64_t k_lo, int64_t k_hi, f32x16& acc, float* As, float* Bs) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wy = wave >> 1, wx = wave & 1, r32 = lane & 31, kh = lane >> 5;
+    f32x16 sum, comp;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sum[r] = comp[r] = 0.f;
     for (int64_t kc = k_lo; kc < k_hi; kc += CH_NB) {
         __syncthreads();                                   // the previous chunk's operands are consumed
         for (int e = tid; e < CH_NB * CH_NB; e += 256) {
@@ -449,14 +461,23 @@ static __device__ __forceinline__ void tile_gemm(const float* __restrict__ Ap, i
         __syncthreads();
         const float* A2 = &As[(32 * wy + r32) * CH_PK + 2 * kh];
         const float* B2 = &Bs[(32 * wx + r32) * CH_PK + 2 * kh];
+        f32x16 part;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[r] = 0.f;
 #pragma unroll
         for (int q = 0; q < CH_NB / 4; ++q) {
             const f32x2 av = *(const f32x2*)(A2 + 4 * q);
             const f32x2 bv = *(const f32x2*)(B2 + 4 * q);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv[1], acc, 0, 0, 0);
+            part = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], bv[0], part, 0, 0, 0);
+            part = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], bv[1], part, 0, 0, 0);
         }
+        // two-sum: s + e == sum + part exactly
+        const f32x16 s = sum + part;
+        const f32x16 bp = s - sum;
+        comp += (sum - (s - bp)) + (part - bp);
+        sum = s;
     }
+    acc = sum + comp;
 }
 
 // level of the doubling: pair z owns the diagonal blocks A = [2 z s, 2 z s + s) and B = [2 z s + s,
@@ -474,8 +495,6 @@ __global__ __launch_bounds__(256) void trinv_level_kernel(const float* __restric
     if (mb <= 0 || ti >= mb) return;
     float* Tp = T + (int64_t)blockIdx.z * s * s;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const int64_t rows = mb - ti < CH_NB ? mb - ti : CH_NB;
     if constexpr (MODE == 0) {
         // T[ti.., tj..] = sum_{k >= tj} L[b0 + ti.., a0 + k] X[a0 + k, a0 + tj..]
@@ -507,8 +526,6 @@ __global__ __launch_bounds__(256) void lauum_kernel(const float* __restrict__ X,
     __shared__ __attribute__((aligned(16))) float Bs[CH_NB * CH_PK];
     const int64_t i0 = (int64_t)I * CH_NB, j0 = (int64_t)J * CH_NB;
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     const int64_t rows = n - i0 < CH_NB ? n - i0 : CH_NB, cols = n - j0 < CH_NB ? n - j0 : CH_NB;
     // A^T[i][t] = X[t][i0 + i] (stored [t][i]); B[t][j] = X[t][j0 + j]; t from i0 (X[t][i] = 0 for t < i)
     tile_gemm<true>(X + i0 * ldx + i0, ldx, rows, X + i0 * ldx + j0, ldx, cols, 0, n - i0, acc, As, Bs);

@@ -7,8 +7,10 @@ Host-side mirror of LAVIS/lavis/compression/pruners/sparsegpt_pruner.py:
 
 The Hessian update of fp16 / bf16 activations is a hand-written MFMA SYRK
 (`ecoflap_hessian_accum`, csrc/syrk.hip; fp32 activations and the trailing update are plain
-library GEMMs, torch.addmm -> hipBLASLt) and the factorisations are rocSOLVER calls; the per-block threshold + sequential sweep, which torch
-runs as ~1000 small kernels per 128 columns, is one fused HIP step
+library GEMMs, torch.addmm -> hipBLASLt); the two damped Cholesky factorisations and the
+inverse from the factor are the build's own fp32 kernels (csrc/cholesky.hip; torch.linalg's
+with `SparseGPT.use_own_cholesky = False`); the per-block threshold + sequential sweep, which
+torch runs as ~1000 small kernels per 128 columns, is one fused HIP step
 (`ecoflap_sparsegpt_block`, csrc/sparsegpt.hip).
 """
 import math
@@ -86,6 +88,8 @@ class SparseGPT:
             self.kernels.hessian_accum(self.H, x, self.nsamples, b)
         self.nsamples += b
 
+    # The reference's expression as it stands: torch.quantile takes at most 2^24 elements, so above
+    # 4096 columns a Hessian that holds an inf raises here, as it does in the reference.
     @staticmethod
     def _clamp_inf(H):
         if (torch.isinf(H) * (H > 0)).float().sum() > 0:          # (:104-112, :136-144)
@@ -95,10 +99,12 @@ class SparseGPT:
 
     # The two Cholesky factorisations by this build's own blocked fp32 kernel (csrc/cholesky.hip,
     # round 6) where the backend has one: rocSOLVER's potrf is latency-bound at these sizes (4-20 ms
-    # where the flops are worth 0.1-1.5) and not safe with two calls in flight.  The factor agrees
-    # with the library's to a few 1e-7 relative — fp32 factorisations re-associate — not bit for
-    # bit: the tests that hold the HIP backend to the oracle backend BIT FOR BIT switch this off so
-    # that both sides factor with the same library call (as they do for `use_mfma_hessian`).
+    # where the flops are worth 0.1-1.5) and not safe with two calls in flight.  Against the fp64
+    # result, up to n = 6144: the factor is within 3-5e-7 of its scale and the inverse within
+    # 6-9e-7 (the library: 4-6e-7 and 0.6-1.2e-6; the inverse's long sums are compensated, see
+    # cholesky.hip), not bit for bit the library's — fp32 factorisations re-associate: the tests
+    # that hold the HIP backend to the oracle backend BIT FOR BIT switch this off so that both
+    # sides factor with the same library call (as they do for `use_mfma_hessian`).
     use_own_cholesky = True
 
     def _cholesky_inverse(self, L):

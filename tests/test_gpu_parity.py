@@ -1630,16 +1630,17 @@ def test_sparsegpt_pruners_hip_equals_oracle(kern, golden_dir, tag, monkeypatch)
 
 
 @pytest.mark.parametrize("upper", [False, True])
-@pytest.mark.parametrize("n", [1, 5, 64, 65, 130, 200, 768, 1408, 2048])
+@pytest.mark.parametrize("n", [1, 5, 64, 65, 130, 200, 768, 1408, 2048, 4100, 5120, 6144])
 def test_own_cholesky_vs_the_library_and_fp64(kern, n, upper):
     """ecoflap_cholesky_f32 (csrc/cholesky.hip; sparsegpt_pruner.py:113-123, :146-155) against
     torch.linalg.cholesky on the same fp32 matrix and against the fp64 factor: its error is of the
     size of the library's own (both are fp32 factorisations of the same matrix: they re-associate,
     they do not agree bit for bit), the other triangle is exactly zero, the input is untouched, a
-    second call gives the same bits.  Sizes with ragged last blocks, one below the block size."""
+    second call gives the same bits.  Sizes with ragged last blocks, one below the block size, and
+    the widths BLIP-2's SparseGPT factors (5120: T5 `wo`, 6144: ViT-g `fc2`)."""
     g = torch.Generator().manual_seed(100 + n)
-    X = torch.randn(n, 2 * n + 3, generator=g)
-    H = (X @ X.t() / (2 * n + 3) + 0.05 * torch.eye(n)).cuda()
+    X = torch.randn(n, 2 * n + 3, generator=g).cuda()
+    H = X @ X.t() / (2 * n + 3) + 0.05 * torch.eye(n, device="cuda")
     H = ((H + H.t()) / 2).contiguous()
     keep = H.clone()
     L, info = kern.cholesky(H, upper=upper)
@@ -1657,14 +1658,27 @@ def test_own_cholesky_vs_the_library_and_fp64(kern, n, upper):
     assert info2 == 0 and torch.equal(L.view(torch.int32), L2.view(torch.int32))
 
 
-@pytest.mark.parametrize("n", [1, 5, 64, 65, 130, 200, 768, 1000, 1408, 2048])
-def test_own_cholesky_inverse_vs_the_library_and_fp64(kern, n):
+_INVERSE_CASES = ([(n, "ridge") for n in (1, 5, 64, 65, 130, 200, 768, 1000, 1408, 2048, 4100, 5120, 6144)]
+                  + [(n, "tokens") for n in (768, 2048, 4100, 5120, 6144)])
+
+
+@pytest.mark.parametrize("n,form", _INVERSE_CASES,
+                         ids=[str(n) if f == "ridge" else f"{n}-{f}" for n, f in _INVERSE_CASES])
+def test_own_cholesky_inverse_vs_the_library_and_fp64(kern, n, form):
     """ecoflap_cholesky_inverse_f32 (torch.cholesky_inverse, sparsegpt_pruner.py:134) against the
     library's result on the same factor and against the fp64 inverse: an error of the library's
-    size, exactly symmetric, repeatable; ragged last blocks and odd numbers of diagonal blocks."""
+    size, exactly symmetric, repeatable; ragged last blocks and odd numbers of diagonal blocks.
+    "ridge": n x (2n + 3) samples and 0.05 I; "tokens": the form of a calibration Hessian (4n
+    tokens of n channels, 0.01 I).  At 5120 / 6144 the product X^T X sums 5000+ terms per entry:
+    with one fp32 accumulator over the whole range (before tile_gemm's chunked two-sum) the
+    "tokens" Hessians came out 6-7e-6 off, 5-6x the library's error and over the bound."""
     g = torch.Generator().manual_seed(300 + n)
-    X = torch.randn(n, 2 * n + 3, generator=g)
-    H = (X @ X.t() / (2 * n + 3) + 0.05 * torch.eye(n)).cuda()
+    if form == "ridge":
+        X = torch.randn(n, 2 * n + 3, generator=g).cuda()
+        H = X @ X.t() / (2 * n + 3) + 0.05 * torch.eye(n, device="cuda")
+    else:
+        X = torch.randn(4 * n, n, generator=g).cuda()
+        H = X.t() @ X / (4 * n) + 0.01 * torch.eye(n, device="cuda")
     H = ((H + H.t()) / 2).contiguous()
     L = torch.linalg.cholesky(H)
     own = kern.cholesky_inverse(L)
@@ -1791,6 +1805,235 @@ def test_own_factor_chain_is_no_worse_than_the_librarys_when_ill_conditioned(ker
     scale = float(ref.abs().max())
     e_own, e_lib = float((U.double() - ref).abs().max()) / scale, float((U_lib.double() - ref).abs().max()) / scale
     assert e_own <= 5 * e_lib + 1e-6 and e_own < 0.05, (e_own, e_lib)
+
+
+# ---- SparseGPT's factorisations at the widths BLIP-2 factors (ViT-g fc2 6144, T5 wo 5120) ------------
+def _hessian_through_add_batch(kern, cols, dt, samples, tokens, seed, rows=16):
+    """A SparseGPT whose H comes from `add_batch` with 16-bit activations (the MFMA Hessian, as in
+    the product), more tokens than columns, channel scales spread over e^(+-1), and ~1 % dead input
+    channels (zero activations there: the reference's `H[dead, dead] = 1`, sparsegpt_pruner.py:98-99)."""
+    from ecoflap_amd.pruners.sparsegpt import SparseGPT
+    g = torch.Generator().manual_seed(seed)
+    scale = torch.exp(0.3 * torch.randn(cols, generator=g))
+    dead = torch.randperm(cols, generator=g)[: cols // 100]
+    scale[dead] = 0
+    sp = SparseGPT(torch.nn.Linear(cols, rows, bias=False).cuda(), kernels=kern)
+    assert sp.use_mfma_hessian
+    for _ in range(samples):
+        sp.add_batch((torch.randn(1, tokens, cols, generator=g) * scale).to(dt).cuda(), None)
+    sp.flush()
+    assert sp.nsamples == samples and int((torch.diag(sp.H) == 0).sum()) == dead.numel()
+    return sp
+
+
+def _fp64_factor_chain(H, percdamp=.01):
+    """sparsegpt_pruner.py:97-155 restated in fp64: dead columns, the inf clamps, the damped lower
+    Cholesky, cholesky_inverse, the damped upper Cholesky of the inverse.  -> (dead, Hinv), fp64."""
+    H = H.double().clone()
+
+    # (as the reference and SparseGPT._clamp_inf: torch.quantile takes at most 2^24 elements, so
+    # past 4096 columns an inf would make this raise, as it would there; no Hessian here holds one)
+    def clamp_inf(H):
+        if (torch.isinf(H) * (H > 0)).float().sum() > 0:
+            H[torch.isinf(H) * (H > 0)] = torch.quantile(H, 0.999)
+        if (torch.isinf(H) * (H < 0)).float().sum() > 0:
+            H[torch.isinf(H) * (H < 0)] = torch.quantile(H, 0.001)
+
+    def damped(H, damp, upper):
+        diag = torch.arange(H.shape[0], device=H.device)
+        for _ in range(1000):
+            L, info = torch.linalg.cholesky_ex(H, upper=upper)
+            if int(info) == 0 and not torch.isnan(L).any():
+                return L
+            H[diag, diag] += damp
+        raise AssertionError("the fp64 chain did not converge")
+
+    dead = torch.diag(H) == 0
+    H[dead, dead] = 1
+    clamp_inf(H)
+    H = damped(H, percdamp * torch.mean(torch.diag(H)), upper=False)
+    H = torch.cholesky_inverse(H)
+    clamp_inf(H)
+    return dead, damped(H, percdamp * torch.mean(torch.diag(H).abs()), upper=True)
+
+
+@pytest.mark.parametrize("cols,dt,samples,tokens", [(1408, torch.float16, 8, 257), (2048, torch.bfloat16, 8, 384),
+                                                    (5120, torch.bfloat16, 24, 256), (6144, torch.float16, 32, 257)])
+def test_own_factor_chain_at_product_widths_vs_fp64(kern, cols, dt, samples, tokens):
+    """`SparseGPT._factor_alone` — the chain of sparsegpt_pruner.py:97-155 on the build's own kernels
+    (the default) and on torch.linalg's — against the same chain in fp64, from one MFMA Hessian with
+    dead columns at the widths BLIP-2 prunes: the own upper factor of Hinv is within 4x the
+    library's error (or 5e-6 of its scale), and both find the same dead columns."""
+    sp = _hessian_through_add_batch(kern, cols, dt, samples, tokens, seed=cols)
+    H0 = sp.H.clone()
+    dead64, U64 = _fp64_factor_chain(H0)
+    U = {}
+    for own in (True, False):
+        sp.H, sp.factor, sp.use_own_cholesky = H0.clone(), None, own
+        sp._factor_alone(.01)
+        dead, U[own] = sp.factor
+        assert torch.equal(dead, dead64)
+        assert U[own].dtype == torch.float32 and bool(torch.isfinite(U[own]).all())
+    scale = float(U64.abs().max())
+    e_own, e_lib = (float((U[o].double() - U64).abs().max()) / scale for o in (True, False))
+    print(f"factor chain at {cols}: own {e_own:.2e}, library {e_lib:.2e} of the fp64 factor's scale")
+    assert e_own <= max(4 * e_lib, 5e-6), (e_own, e_lib)
+
+
+@pytest.mark.parametrize("rows,cols,dt,samples,tokens", [(1408, 6144, torch.float16, 32, 257),
+                                                         (2048, 5120, torch.bfloat16, 24, 256)])
+def test_fasterprune_at_true_width_against_the_fp64_factor(kern, rows, cols, dt, samples, tokens):
+    """`SparseGPT.fasterprune` on ViT-g `fc2` (1408 x 6144, fp16) and T5 `wo` (2048 x 5120, bf16) at
+    sparsity 0.5 and 2:4, from the same H and weights three times: with the own factorisations (the
+    default), with torch.linalg's, and with the fp64 chain's factor rounded to fp32 (handed in as
+    `factor`).  Against the fp64-factor run: the own run's masks differ in at most 1e-3 of the
+    entries and at most 2x as many as the library run's (+ 1e-4 of the entries); in rows whose mask
+    is the reference's, the kept weights agree to 1e-4 of the matrix' scale.  (The Linear is fp32
+    holding 16-bit values, so the weights are compared before the cast back to 16 bits, whose one
+    ulp is 1e-3 of the scale.)"""
+    from ecoflap_amd.pruners.sparsegpt import SparseGPT
+    sp0 = _hessian_through_add_batch(kern, cols, dt, samples, tokens, seed=rows + cols)
+    H0, nsamples = sp0.H, sp0.nsamples
+    sp0.H = None
+    dead64, U64 = _fp64_factor_chain(H0)
+    fp64_factor = (dead64, U64.float().contiguous())
+    del U64
+    g = torch.Generator().manual_seed(rows)
+    w0 = (torch.randn(rows, cols, generator=g) * 0.02).to(dt).float().cuda()
+    for sparsity, pn, pm in ((0.5, 0, 0), (0.5, 2, 4)):
+        out = {}
+        for chain in ("own", "library", "fp64"):
+            lin = torch.nn.Linear(cols, rows, bias=False).cuda()
+            with torch.no_grad():
+                lin.weight.copy_(w0)
+            sp = SparseGPT(lin, kernels=kern)
+            sp.H, sp.nsamples = H0.clone(), nsamples
+            sp.use_own_cholesky = chain == "own"
+            if chain == "fp64":
+                sp.factor = fp64_factor
+            sp.fasterprune(sparsity, prune_n=pn, prune_m=pm)
+            out[chain] = lin.weight.data.clone()
+            del sp, lin
+        ref = out["fp64"]
+        assert abs(float((ref == 0).float().mean()) - 0.5) < 0.01
+        flips = {c: int(((out[c] == 0) != (ref == 0)).sum()) for c in ("own", "library")}
+        same_rows = ((out["own"] == 0) == (ref == 0)).all(dim=1)
+        print(f"fasterprune {rows}x{cols} {'%d:%d' % (pn, pm) if pn else sparsity}: mask flips against the "
+              f"fp64 factor's run: own {flips['own']}, library {flips['library']} of {ref.numel()}; "
+              f"{int(same_rows.sum())} of {rows} rows unchanged")
+        assert flips["own"] <= 1e-3 * ref.numel(), flips
+        assert flips["own"] <= 2 * flips["library"] + 1e-4 * ref.numel(), flips
+        assert int(same_rows.sum()) > 0
+        assert float((out["own"] - ref)[same_rows].abs().max()) <= 1e-4 * float(ref.abs().max())
+
+
+def _hessian_with_known_spectrum(n, lam_min_in_damps, seed, percdamp=.01):
+    """A symmetric n x n Hessian (fp32) whose smallest eigenvalue is `lam_min_in_damps` x damp, damp =
+    percdamp x mean(diag) (the reference's, sparsegpt_pruner.py:114): a well-conditioned SPD block
+    (eigenvalues >= 0.5) next to a 64 x 64 block Q diag(lam) Q^T with lam[1:] in [0.5, 1.5), then one
+    symmetric permutation that scatters the 64 special indices (the spectrum does not move)."""
+    g = torch.Generator().manual_seed(seed)
+    m = n - 64
+    G = torch.randn(m, 512, generator=g, dtype=torch.float64).cuda()
+    A = G @ G.t() / 512 + 0.5 * torch.eye(m, dtype=torch.float64, device="cuda")
+    lam = 0.5 + torch.rand(64, generator=g, dtype=torch.float64)
+    c = percdamp * lam_min_in_damps
+    lam[0] = c * (float(A.diagonal().sum()) + float(lam[1:].sum())) / (n - c)    # = c * trace(H) / n
+    Q, _ = torch.linalg.qr(torch.randn(64, 64, generator=g, dtype=torch.float64))
+    H = torch.zeros(n, n, dtype=torch.float64, device="cuda")
+    H[:m, :m] = A
+    H[m:, m:] = ((Q * lam) @ Q.t()).cuda()
+    perm = torch.randperm(n, generator=g).cuda()
+    H = H[perm][:, perm]
+    return ((H + H.t()) / 2).float().contiguous()
+
+
+@pytest.mark.parametrize("upper", [False, True])
+@pytest.mark.parametrize("n", [1408, 6144])
+@pytest.mark.parametrize("lam_min,rounds", [(0.5, 0), (-2.5, 3), (-0.5, 1)])
+def test_damped_cholesky_takes_the_same_damping_rounds_as_the_library(kern, n, upper, lam_min, rounds):
+    """`SparseGPT._damped_cholesky` (sparsegpt_pruner.py:113-123 / :146-155: add damp to the diagonal
+    until the factorisation succeeds) on the own kernel and on torch.linalg's, on Hessians whose
+    smallest eigenvalue lies 0.5 damp off a decision (no round, one, three): both take exactly the
+    expected number of rounds — H's diagonal after the call (damped in place) is bit-equal between
+    the two and to `rounds` fp32 adds of damp — and both factors reconstruct the damped H."""
+    from ecoflap_amd.pruners.sparsegpt import SparseGPT
+    H = _hessian_with_known_spectrum(n, lam_min, seed=n + int(4 * lam_min))
+    damp = .01 * torch.mean(torch.diag(H))
+    want = torch.diag(H).clone()
+    for _ in range(rounds):
+        want += damp
+    diags = {}
+    for own in (True, False):
+        sp = SparseGPT(torch.nn.Linear(8, 1, bias=False).cuda(), kernels=kern)
+        sp.use_own_cholesky = own
+        Hc = H.clone()
+        L = sp._damped_cholesky(Hc, damp, upper=upper)
+        diags[own] = torch.diag(Hc).clone()
+        assert bool(torch.isfinite(L).all())
+        back = (L.t() @ L) if upper else (L @ L.t())
+        assert float((back - Hc).abs().max()) <= 2e-5 * float(Hc.abs().max())
+    assert torch.equal(diags[True], diags[False])
+    assert torch.equal(diags[True], want), float(((diags[True] - torch.diag(H)) / damp).mean())
+
+
+@pytest.mark.parametrize("upper", [False, True])
+@pytest.mark.parametrize("n", [1408, 6144])
+def test_damped_cholesky_of_a_rank_deficient_hessian(kern, n, upper):
+    """Fewer tokens than columns: H is singular and whether the undamped factorisation passes is a
+    coin flip of rounding for either path.  Each path returns a finite factor (info == 0 inside the
+    loop) after at most two damping rounds, and the factor reconstructs its own damped H."""
+    from ecoflap_amd.pruners.sparsegpt import SparseGPT
+    g = torch.Generator().manual_seed(7 + n)
+    t = n // 4
+    x = torch.randn(t, n, generator=g).cuda()
+    H = (x.t() @ x * (2.0 / t)).contiguous()
+    H = ((H + H.t()) / 2).contiguous()
+    damp = .01 * torch.mean(torch.diag(H))
+    for own in (True, False):
+        sp = SparseGPT(torch.nn.Linear(8, 1, bias=False).cuda(), kernels=kern)
+        sp.use_own_cholesky = own
+        Hc = H.clone()
+        L = sp._damped_cholesky(Hc, damp, upper=upper)
+        k = round(float(((torch.diag(Hc) - torch.diag(H)) / damp).mean()))
+        assert 0 <= k <= 2, (own, k)
+        assert bool(torch.isfinite(L).all())
+        back = (L.t() @ L) if upper else (L @ L.t())
+        assert float((back - Hc).abs().max()) <= 2e-5 * float(Hc.abs().max()), (own, k)
+
+
+@pytest.mark.parametrize("widths", [(1408, 1408, 1408, 6144), (2048, 2048, 2048, 5120)])
+def test_factor_all_side_by_side_at_true_widths_equals_one_by_one(kern, widths, monkeypatch):
+    """`SparseGPT.factor_all` with the block's factorisations side by side on per-thread streams (the
+    default) gives the factors of the one-by-one form bit for bit, at a ViT-g block's widths (three
+    1408 + one 6144) and a T5 block's (2048s + one 5120), dead columns included."""
+    from ecoflap_amd.pruners.sparsegpt import SparseGPT
+    monkeypatch.setattr(SparseGPT, "use_own_cholesky", True)
+    g = torch.Generator().manual_seed(sum(widths))
+    Hs = []
+    for cols in widths:
+        t = cols + 256
+        x = torch.randn(t, cols, generator=g)
+        x[:, torch.randperm(cols, generator=g)[: cols // 100]] = 0
+        x = x.cuda()
+        Hs.append((x.t() @ x * (2.0 / t)).contiguous())
+
+    def factors(side):
+        monkeypatch.setattr(SparseGPT, "side_by_side", side)
+        items = []
+        for cols, H in zip(widths, Hs):
+            sp = SparseGPT(torch.nn.Linear(cols, 8, bias=False).cuda(), kernels=kern)
+            sp.H, sp.nsamples = H.clone(), 1
+            items.append(sp)
+        SparseGPT.factor_all(items)
+        torch.cuda.synchronize()
+        return [sp.factor for sp in items]
+
+    alone = factors(False)
+    for _ in range(2):
+        for (d0, U0), (d1, U1) in zip(alone, factors(True)):
+            assert torch.equal(d0, d1) and int(d0.sum()) > 0
+            assert torch.equal(U0.view(torch.int32), U1.view(torch.int32))
 
 
 # ------------------------------------------------------------------------------ Real-* (global)
