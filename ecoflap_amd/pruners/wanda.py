@@ -397,15 +397,60 @@ class _BlockwiseWanda:
         graphed = graphed_plain and getattr(self.owner, "local_method", "wanda") != "sparsegpt"
         # Batch-1 calibration samples (the launchers' default) leave a replayed block forward at
         # ~40 kernels of a few microseconds: G samples ride one replay where the block gives
-        # every slot of the stacked input the bits it gives that sample alone (checked on the
-        # first group of every block: slots 0 and G-1 against their batch-1 forwards; a part
-        # whose check fails once goes back to one replay per sample).  round 6: 7.1 s of
+        # every slot of the stacked input the bits it gives that sample alone.  The slot guard
+        # holds every grouped pass to that: in the first group of a block ALL G slots, in each
+        # later group g the slot (3 g + 1) mod G (every slot within G groups for G = 8), against
+        # batch-1 replays of the block — the block output (pass after the prune) or every
+        # Linear's input rows (SparseGPT's hooked pass).  The comparisons accumulate in one device
+        # flag, read once per block; a block whose flag is set throws its grouped results away,
+        # runs again one replay per sample, and the part never groups again.  round 6: 7.1 s of
         # SparseGPT's 15 s of stage 2 on the BLIP-2 shape were these forwards.
         G = int(getattr(self.owner, "stage2_group", 8))
         min_values = int(getattr(self.owner, "stage2_group_min_values", 65536))
         group_ok = [graphed_plain and G > 1 and int(inps[0].shape[0]) == 1 and n_batches >= 2 * G
                     and all((not torch.is_tensor(v)) or (v.dim() > 0 and int(v.shape[0]) == 1)
                             for v in caches[0].values())]
+        # per part: passes that kept their grouped results, slots compared, where a check failed
+        guard = (self.owner.stage_stats.setdefault("stage2_group_guard", {}).setdefault(
+            module_to_process, {"grouped_passes": 0, "slot_checks": 0, "fell_back": None})
+            if group_ok[0] else None)
+
+        def checked_slots(g, verify_all):
+            return range(G) if g == 0 or verify_all else ((3 * g + 1) % G,)
+
+        def capture_one(block):
+            """A batch-1 graph of `block` -> (graph, static input, static kwargs, output): the
+            forward each slot of a grouped replay is held to (warmed up by the caller)."""
+            x1 = inps[0].clone()
+            kw1 = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in caches[0].items()}
+            graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), capture_graph(graph, capture_error_mode="thread_local"):
+                with autocast():
+                    y = block(x1, **kw1)
+                y = y[0] if take_first else y
+            return graph, x1, kw1, y
+
+        def replay_one(one, j):
+            from ..shapes import fused
+            graph, x1, kw1, _ = one
+            fused.multi_copy([(x1, inps[j])] + [(kw1[k], v) for k, v in caches[j].items()
+                                                  if torch.is_tensor(v)])
+            graph.replay()
+
+        def guard_passed(flag, checks, block_i, which):
+            """The block's one read of the slot guard's flag -> True: every checked slot agreed.
+            (Synchronises the stream: the caller's graphs may go away after it.)"""
+            torch.cuda.current_stream().synchronize()
+            guard["slot_checks"] += checks
+            if int(flag.item()) == 0:
+                return True
+            guard["fell_back"] = f"block {block_i}, {which} pass"
+            return False
+
+        def count_grouped():
+            guard["grouped_passes"] += 1
+            self.owner.stage_stats["stage2_grouped_passes"] = (
+                self.owner.stage_stats.get("stage2_grouped_passes", 0) + 1)
 
         def stacked_inputs():
             sx = torch.cat([inps[j] for j in range(G)], 0)
@@ -422,10 +467,13 @@ class _BlockwiseWanda:
                 pairs += [(skw[k][i:i + 1], v) for k, v in caches[j].items() if torch.is_tensor(v)]
             fused.multi_copy(pairs)
 
-        def graph_pass_grouped(block):
-            """The plain pass (no hooks) with G samples per replay -> False: not slot invariant
-            here (nothing kept; the caller runs `graph_pass`)."""
-            y_first, y_last = call(block, 0), call(block, G - 1)
+        def graph_pass_grouped(block, block_i):
+            """The plain pass (no hooks) with G samples per replay, under the slot guard -> False:
+            a checked slot's output differs from its batch-1 replay (the caller runs
+            `graph_pass`, which writes every output again)."""
+            from ..shapes import fused
+            call(block, 0)                                        # warm-up at batch 1
+            one = capture_one(block)
             sx, skw = stacked_inputs()
             with torch.no_grad(), autocast():
                 block(sx, **skw)                                  # warm-up at this width
@@ -434,46 +482,41 @@ class _BlockwiseWanda:
                 with autocast():
                     y = block(sx, **skw)
                 y = y[0] if take_first else y
-            graph.replay()
-            if not (torch.equal(y[0:1], y_first) and torch.equal(y[G - 1:G], y_last)):
-                torch.cuda.current_stream().synchronize()
-                del graph
-                return False
-            # too few values for two slots to rule out a lucky agreement (toy shapes: a handful
-            # of short dot products round alike in two kernels most of the time): every sample
-            # is then also run alone and compared, and the first difference ends the grouping
-            verify_all = 2 * y_first.numel() < min_values
-            n_full = n_batches // G
-            rest_from = n_full * G
+            # too few values for one slot per group to rule out a lucky agreement (toy shapes: a
+            # handful of short dot products round alike in two kernels most of the time): every
+            # slot of every group is then compared
+            verify_all = 2 * one[3].numel() < min_values
+            flag = torch.zeros(1, dtype=torch.int32, device=y.device)
+            n_full, checks = n_batches // G, 0
             for g in range(n_full):
                 if g:
                     load_group(sx, skw, g)
-                    graph.replay()
+                graph.replay()
                 yc = y.clone()
-                if verify_all:
-                    alone = [call(block, g * G + i) for i in range(G)]
-                    if not all(torch.equal(yc[i:i + 1], alone[i]) for i in range(G)):
-                        for i in range(G):
-                            outs[g * G + i] = alone[i]
-                        rest_from, group_ok[0] = (g + 1) * G, False
-                        break
                 for i in range(G):
                     outs[g * G + i] = yc[i:i + 1]
-            for j in range(rest_from, n_batches):
+                for i in checked_slots(g, verify_all):
+                    replay_one(one, g * G + i)
+                    fused.multi_compare([(yc[i:i + 1], one[3])], flag)
+                    checks += 1
+            ok = guard_passed(flag, checks, block_i, "plain")
+            del graph, one                                # (after the synchronisation)
+            if not ok:
+                return False
+            for j in range(n_full * G, n_batches):
                 outs[j] = call(block, j)
-            torch.cuda.current_stream().synchronize()     # the graph's buffers go away with it
-            del graph
-            self.owner.stage_stats["stage2_grouped_passes"] = (
-                self.owner.stage_stats.get("stage2_grouped_passes", 0) + 1)
+            count_grouped()
             return True
 
-        def graph_pass_hessian_grouped(block, wrapped):
+        def graph_pass_hessian_grouped(block, wrapped, block_i):
             """SparseGPT's hooked pass with G = `samples_per_call` samples per replay: the static
             input each Linear read IS the concatenated [G x tokens, cols] operand of one
             `hessian_accum` call — the calls, their rows and their order are those of
-            `graph_pass_hessian`.  Checked per block: every Linear's rows of slot 0 and of slot
-            G-1 against the inputs it sees in batch-1 forwards of samples 0 and G-1.
-            -> False (nothing accumulated) when they differ or a Linear is off the MFMA path."""
+            `graph_pass_hessian`.  Under the slot guard: each checked slot's rows of every Linear
+            against the input that Linear reads in a batch-1 replay of the block.
+            -> False with nothing accumulated (H zero, no samples counted) when a checked slot
+            differs or a Linear is off the MFMA path."""
+            from ..shapes import fused
             from .sparsegpt import SparseGPT
             if G != int(SparseGPT.samples_per_call):
                 return False
@@ -489,10 +532,10 @@ class _BlockwiseWanda:
             for name, w_ in wrapped.items():
                 w_.add_batch = noting(name)
             try:
-                call(block, 0)
-                ref_first, seen = seen, {}
-                call(block, G - 1)
-                ref_last, seen = seen, {}
+                call(block, 0)                                    # warm-up at batch 1
+                seen = {}
+                one = capture_one(block)
+                ref, seen = seen, {}                              # each Linear's input, batch 1
                 sx, skw = stacked_inputs()
                 with torch.no_grad(), autocast():
                     block(sx, **skw)                              # warm-up at this width
@@ -502,48 +545,42 @@ class _BlockwiseWanda:
                     with autocast():
                         block(sx, **skw)
                 static, seen = seen, {}
-                graph.replay()
-                ok = set(static) == set(wrapped) == set(ref_first)
+                ok = set(static) == set(wrapped) == set(ref)
                 for name in (static if ok else ()):
-                    t = ref_first[name].shape[0]
-                    ok = (ok and static[name].shape[0] == G * t
-                          and static[name].dtype in (torch.float16, torch.bfloat16)
-                          and torch.equal(static[name][:t], ref_first[name])
-                          and torch.equal(static[name][(G - 1) * t:], ref_last[name]))
+                    ok = (ok and static[name].shape == (G * ref[name].shape[0],) + ref[name].shape[1:]
+                          and static[name].dtype in (torch.float16, torch.bfloat16))
                 if not ok:
                     torch.cuda.current_stream().synchronize()
-                    del graph
+                    del graph, one
                     return False
-                verify_all = 2 * sum(v.numel() for v in ref_first.values()) < min_values   # (see graph_pass_grouped)
-                n_full = n_batches // G
-                rest_from = n_full * G
+                verify_all = 2 * sum(v.numel() for v in ref.values()) < min_values   # (see graph_pass_grouped)
+                flag = torch.zeros(1, dtype=torch.int32, device=sx.device)
+                n_full, checks = n_batches // G, 0
                 for g in range(n_full):
                     if g:
                         load_group(sx, skw, g)
-                        graph.replay()
-                    if verify_all:
-                        same = True
-                        for i in range(G):
-                            seen = {}
-                            call(block, g * G + i)               # the noting hooks: this sample alone
-                            same = same and all(
-                                torch.equal(static[n][i * seen[n].shape[0]:(i + 1) * seen[n].shape[0]], seen[n])
-                                for n in static)
-                        if not same:
-                            rest_from, group_ok[0] = g * G, False
-                            break
+                    graph.replay()
                     for name, w_ in wrapped.items():
                         w_.kernels.hessian_accum(w_.H, static[name], w_.nsamples, G)
                         w_.nsamples += G
+                    for i in checked_slots(g, verify_all):
+                        replay_one(one, g * G + i)
+                        fused.multi_compare([(static[n][i * ref[n].shape[0]:(i + 1) * ref[n].shape[0]], ref[n])
+                                             for n in static], flag)
+                        checks += 1
+                ok = guard_passed(flag, checks, block_i, "hooked")
+                del graph, one                            # (after the synchronisation)
             finally:
                 for w_ in wrapped.values():
                     del w_.add_batch
-            for j in range(rest_from, n_batches):
+            if not ok:
+                for w_ in wrapped.values():
+                    w_.H.zero_()
+                    w_.nsamples = 0
+                return False
+            for j in range(n_full * G, n_batches):
                 call(block, j)                                    # the ordinary hooks; flushed by the caller
-            torch.cuda.current_stream().synchronize()
-            del graph
-            self.owner.stage_stats["stage2_grouped_passes"] = (
-                self.owner.stage_stats.get("stage2_grouped_passes", 0) + 1)
+            count_grouped()
             return True
 
         def graph_pass(block, wrapped, keep):
@@ -699,8 +736,8 @@ class _BlockwiseWanda:
                 hess_graphs = sparsegpt and graphed_plain and getattr(self.owner, "sparsegpt_graph_hooks", True)
                 grouped = False
                 if hess_graphs and group_ok[0]:
-                    grouped = graph_pass_hessian_grouped(block, wrapped)
-                    group_ok[0] = grouped
+                    grouped = graph_pass_hessian_grouped(block, wrapped, i)
+                    group_ok[0] = group_ok[0] and grouped      # a failed check: off for the part
                 if graphed:
                     graph_pass(block, wrapped, keep=False)
                 elif grouped:
@@ -772,7 +809,7 @@ class _BlockwiseWanda:
                 for w_ in wrapped.values():
                     w_.free()
             with PhaseTimer.span("stage2.block_forward_after_prune"):
-                if group_ok[0] and graph_pass_grouped(block):
+                if group_ok[0] and graph_pass_grouped(block, i):
                     pass
                 elif graphed_plain:
                     group_ok[0] = False
