@@ -36,6 +36,7 @@ def _get():
         lib.ecoflap_linear_f32.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp]
         lib.ecoflap_qkv_bias_add.argtypes = [vp, vp, vp, i64, i64, ci, vp]
         lib.ecoflap_vit_attention.argtypes = [vp, vp, i64, i64, i64, i64, f32, ci, vp]
+        lib.ecoflap_vit_attention_v1.argtypes = [vp, vp, i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_multi_copy.argtypes = [vp, ci, vp]
         lib.ecoflap_multi_compare.argtypes = [vp, ci, vp, vp]
         _lib = lib
@@ -162,6 +163,16 @@ def vit_attention(qkv, heads, scale):
     one kernel instead of permute / contiguous copies + the library's fused attention (which runs
     the ViT-g shape, 257 tokens x 16 heads of 88, at a few percent of the MFMA rate).
     -> tensor or None (caller runs torch's scaled_dot_product_attention)."""
+    return _vit_attention(qkv, heads, scale, "ecoflap_vit_attention")
+
+
+def vit_attention_v1(qkv, heads, scale):
+    """`vit_attention` on the kernel's previous schedule (`ecoflap_vit_attention_v1`): the same
+    shapes, the same bits; the reference of the bitwise tests and tools/attention_launches.py."""
+    return _vit_attention(qkv, heads, scale, "ecoflap_vit_attention_v1")
+
+
+def _vit_attention(qkv, heads, scale, entry):
     import os
     if (torch.is_grad_enabled() or qkv.device.type != "cuda" or qkv.dtype != torch.float16
             or qkv.dim() != 3 or not qkv.is_contiguous() or os.environ.get("ECOFLAP_NO_FUSED_ATTENTION")):
@@ -173,12 +184,12 @@ def vit_attention(qkv, heads, scale):
     if N > 288 or D > 96 or D % 8 != 0 or D < 8:
         return None
     out = torch.empty((B, N, heads * D), dtype=qkv.dtype, device=qkv.device)
-    rc = _get().ecoflap_vit_attention(qkv.data_ptr(), out.data_ptr(), B, N, heads, D, float(scale),
-                                      _hip.DTYPE_CODE[qkv.dtype], _stream())
+    rc = getattr(_get(), entry)(qkv.data_ptr(), out.data_ptr(), B, N, heads, D, float(scale),
+                                _hip.DTYPE_CODE[qkv.dtype], _stream())
     if rc == -3:        # ECOFLAP_ESIZE: the head's K image does not fit the kernel's LDS buffers
         return None
     if rc != 0:
-        raise _hip.EcoflapHipError(f"ecoflap_vit_attention failed ({rc})")
+        raise _hip.EcoflapHipError(f"{entry} failed ({rc})")
     return out
 
 

@@ -69,6 +69,11 @@ int ecoflap_qkv_bias_add(void* qkv, const float* q_bias, const float* v_bias, in
 int ecoflap_vit_attention(const void* qkv, void* out, int64_t batch, int64_t tokens,
                           int64_t heads, int64_t head_dim, float scale, int dtype, void* stream);
 
+/* ecoflap_vit_attention on the kernel's previous schedule (one 4-wave workgroup per CU): the
+ * same shapes and the same output bits; kept as the reference of the bitwise tests. */
+int ecoflap_vit_attention_v1(const void* qkv, void* out, int64_t batch, int64_t tokens,
+                             int64_t heads, int64_t head_dim, float scale, int dtype, void* stream);
+
 /* Up to ECOFLAP_COPY_MAX_ITEMS device-to-device copies (non-overlapping, any alignment) in
  * one launch: the loop's state hand-overs between static graph buffers. */
 #define ECOFLAP_COPY_MAX_ITEMS 32

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""ViT-g attention at the loop's batch sizes: this build's kernel vs torch's fused attention
-(HIP events, 30 launches each)."""
+"""ViT-g attention at the loop's batch sizes: this build's kernel vs its previous schedule
+(`old_us`, `ecoflap_vit_attention_v1`) and torch's fused attention (HIP events, 30 launches each)."""
 import json
 import os
 import sys
@@ -34,12 +34,13 @@ def main():
         flops = 4.0 * B * H * N * N * D
         with torch.no_grad():
             t_own = timed(lambda: fused.vit_attention(qkv, H, D ** -0.5))
+            t_old = timed(lambda: fused.vit_attention_v1(qkv, H, D ** -0.5))
 
             def lib():
                 q, k, v = qkv.reshape(B, N, 3, H, D).permute(2, 0, 3, 1, 4)
                 return F.scaled_dot_product_attention(q, k, v, scale=D ** -0.5).transpose(1, 2).reshape(B, N, -1)
             t_lib = timed(lib)
-        rows.append({"batch": B, "own_us": round(t_own, 1), "library_us": round(t_lib, 1),
+        rows.append({"batch": B, "own_us": round(t_own, 1), "old_us": round(t_old, 1), "library_us": round(t_lib, 1),
                      "own_tflops": round(flops / t_own / 1e6, 1), "library_tflops": round(flops / t_lib / 1e6, 1),
                      "hbm_bytes": 4 * B * N * H * D * 2,
                      "own_pct_of_8TBs": round(100 * 4 * B * N * H * D * 2 / (t_own * 1e-6) / 8e12, 1)})
