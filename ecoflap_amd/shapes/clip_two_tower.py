@@ -1,8 +1,9 @@
 """Two-tower CLIP shape for the contrastive loss closure (plumbing; CoOp/clip/model.py:336-366
 is the contract: `model(image, text) -> (logits_per_image, logits_per_text)` = `logit_scale.exp()`
 times the cosine similarities of the normalised image and text features, logit_scale initialised
-to log(1/0.07), :291).  Toy towers only: CoOp's OpenAI-CLIP model zoo, its BPE tokenizer and the
-`clip_*_pruner` family are outside the hot path (DESIGN.md \u00a78)."""
+to log(1/0.07), :291).  Toy MLP towers for the closure's tests; the OpenAI-CLIP ViT towers
+themselves are `shapes/clip.py`.  CoOp's BPE tokenizer is outside the hot path and the
+`clip_*_pruner` family is not built yet (DESIGN.md \u00a78)."""
 import math
 
 import torch

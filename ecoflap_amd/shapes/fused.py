@@ -193,6 +193,43 @@ def _vit_attention(qkv, heads, scale, entry):
     return out
 
 
+def mha_attention(qkv, heads, scale, causal=False, seq_first=True):
+    """softmax(q k^T * scale [+ causal mask]) v per (sample, head) straight from the output of an
+    nn.MultiheadAttention in-projection — [L, N, 3 * heads * 64] (`seq_first`, the layout the
+    OpenAI-CLIP blocks keep) or [N, L, 3 * heads * 64], rows [3, heads, 64], any row strides that
+    are multiples of 8 elements (a permuted view needs no copy) — into the merged heads in the
+    same dimension order, [L, N, heads * 64] or [N, L, heads * 64], contiguous
+    (`ecoflap_mha_attention`, csrc/mha_attention.hip).
+    -> tensor or None (caller runs torch's attention): the refusal rules of `vit_attention`, and
+    the shapes the kernel does not serve (head width != 64, more than 224 tokens)."""
+    import os
+    if (torch.is_grad_enabled() or qkv.device.type != "cuda" or qkv.dtype != torch.float16
+            or qkv.dim() != 3 or qkv.stride(2) != 1 or os.environ.get("ECOFLAP_NO_FUSED_ATTENTION")):
+        return None
+    if heads < 1 or qkv.shape[2] != 3 * heads * 64 or not (0.0 < float(scale) < float("inf")):
+        return None
+    t_dim, b_dim = (0, 1) if seq_first else (1, 0)
+    L, B = qkv.shape[t_dim], qkv.shape[b_dim]
+    if not (1 <= L <= 224) or B < 1:
+        return None
+    lib = _get()
+    if not getattr(lib, "_mha_bound", False):
+        vp, i64 = ctypes.c_void_p, ctypes.c_int64
+        lib.ecoflap_mha_attention.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
+                                              ctypes.c_int, ctypes.c_float, ctypes.c_int, vp]
+        lib._mha_bound = True
+    out = torch.empty(qkv.shape[0], qkv.shape[1], heads * 64, dtype=qkv.dtype, device=qkv.device)
+    rc = lib.ecoflap_mha_attention(qkv.data_ptr(), out.data_ptr(), B, L, heads, 64,
+                                   qkv.stride(t_dim), qkv.stride(b_dim), out.stride(t_dim),
+                                   out.stride(b_dim), int(bool(causal)), float(scale),
+                                   _hip.DTYPE_CODE[qkv.dtype], _stream())
+    if rc in (-3, -5):      # ECOFLAP_ESIZE / ECOFLAP_EALIGN: a view the kernel cannot address in place
+        return None
+    if rc != 0:
+        raise _hip.EcoflapHipError(f"ecoflap_mha_attention failed ({rc})")
+    return out
+
+
 class _CopyItem(ctypes.Structure):
     _fields_ = [("dst", ctypes.c_void_p), ("src", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
 

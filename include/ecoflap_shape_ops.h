@@ -74,6 +74,24 @@ int ecoflap_vit_attention(const void* qkv, void* out, int64_t batch, int64_t tok
 int ecoflap_vit_attention_v1(const void* qkv, void* out, int64_t batch, int64_t tokens,
                              int64_t heads, int64_t head_dim, float scale, int dtype, void* stream);
 
+/* Multi-head self-attention of the OpenAI-CLIP towers (CoOp/clip/model.py:167-188: the
+ * nn.MultiheadAttention of a ResidualAttentionBlock between its in- and out-projection), and of
+ * any tower of that shape family: out = softmax(q k^T * scale [+ causal mask]) v per (sample, head)
+ * (csrc/mha_attention.hip).  qkv is the in-projection's output read in place: the row of (sample b,
+ * token n) starts at qkv + b * qkv_batch_stride + n * qkv_token_stride (elements) and holds
+ * [3, heads, head_dim]; out's row of (b, n) starts at out + b * out_batch_stride + n *
+ * out_token_stride and receives the merged heads [heads, head_dim] — so [L, N, 3D] (sequence
+ * first) and [N, L, 3D] both work without a copy.  causal != 0: key j > query i is masked
+ * (probability exactly 0).  F16 only (else ECOFLAP_EDTYPE); head_dim == 64, 1 <= tokens <= 224,
+ * finite scale > 0, token strides at least a row (else ECOFLAP_ESIZE); pointers 16-byte aligned
+ * and every stride a multiple of 8 elements (else ECOFLAP_EALIGN).  fp32 scores / exact two-pass
+ * softmax, probabilities rounded to f16 for the second product; each (sample, head) is computed
+ * independently of the others (batch invariant bit for bit).  Nothing is launched on an error. */
+int ecoflap_mha_attention(const void* qkv, void* out, int64_t batch, int64_t tokens, int64_t heads,
+                          int64_t head_dim, int64_t qkv_token_stride, int64_t qkv_batch_stride,
+                          int64_t out_token_stride, int64_t out_batch_stride, int causal,
+                          float scale, int dtype, void* stream);
+
 /* Up to ECOFLAP_COPY_MAX_ITEMS device-to-device copies (non-overlapping, any alignment) in
  * one launch: the loop's state hand-overs between static graph buffers. */
 #define ECOFLAP_COPY_MAX_ITEMS 32
