@@ -37,6 +37,7 @@ def _get():
         lib.ecoflap_qkv_bias_add.argtypes = [vp, vp, vp, i64, i64, ci, vp]
         lib.ecoflap_vit_attention.argtypes = [vp, vp, i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_vit_attention_v1.argtypes = [vp, vp, i64, i64, i64, i64, f32, ci, vp]
+        lib.ecoflap_mha_attention.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, ci, f32, ci, vp]
         lib.ecoflap_multi_copy.argtypes = [vp, ci, vp]
         lib.ecoflap_multi_compare.argtypes = [vp, ci, vp, vp]
         _lib = lib
@@ -212,17 +213,11 @@ def mha_attention(qkv, heads, scale, causal=False, seq_first=True):
     L, B = qkv.shape[t_dim], qkv.shape[b_dim]
     if not (1 <= L <= 224) or B < 1:
         return None
-    lib = _get()
-    if not getattr(lib, "_mha_bound", False):
-        vp, i64 = ctypes.c_void_p, ctypes.c_int64
-        lib.ecoflap_mha_attention.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
-                                              ctypes.c_int, ctypes.c_float, ctypes.c_int, vp]
-        lib._mha_bound = True
     out = torch.empty(qkv.shape[0], qkv.shape[1], heads * 64, dtype=qkv.dtype, device=qkv.device)
-    rc = lib.ecoflap_mha_attention(qkv.data_ptr(), out.data_ptr(), B, L, heads, 64,
-                                   qkv.stride(t_dim), qkv.stride(b_dim), out.stride(t_dim),
-                                   out.stride(b_dim), int(bool(causal)), float(scale),
-                                   _hip.DTYPE_CODE[qkv.dtype], _stream())
+    rc = _get().ecoflap_mha_attention(qkv.data_ptr(), out.data_ptr(), B, L, heads, 64,
+                                      qkv.stride(t_dim), qkv.stride(b_dim), out.stride(t_dim),
+                                      out.stride(b_dim), int(bool(causal)), float(scale),
+                                      _hip.DTYPE_CODE[qkv.dtype], _stream())
     if rc in (-3, -5):      # ECOFLAP_ESIZE / ECOFLAP_EALIGN: a view the kernel cannot address in place
         return None
     if rc != 0:
