@@ -32,13 +32,19 @@ static __device__ __forceinline__ void at_zero_v_tail(unsigned char* Vs, int N, 
 //   N, D              tokens, head width (D % 8 == 0, D <= 16 * DC)
 //   debug             phase-ablation word of tools/attention_launches.py (2: no QK^T, 4: no
 //                     softmax, 8: no PV, 16: no store)
+//   sqw               COLSQ only: 32 * DT floats (LDS) that receive, per column d of the head, the
+//                     sum over this tile's queries < N of (float)(f16-rounded O[q, d])^2 — the
+//                     sum of squares of exactly the values the store writes; obase may then be
+//                     null (wave-uniform): nothing is stored
 // A caller that passes constants for D, kpitch and debug pays for none of their selects.
-// PREFETCH_V picks the schedule of the V fragment loads (below), not the arithmetic.
-template <int NT, int DC, int DT, bool CAUSAL, bool PREFETCH_V>
+// PREFETCH_V picks the schedule of the V fragment loads (below), not the arithmetic.  COLSQ adds
+// an epilogue and changes nothing before it: the instantiations without it are what they were.
+template <int NT, int DC, int DT, bool CAUSAL, bool PREFETCH_V, bool COLSQ = false>
 static __device__ __forceinline__ void attention_tile(const unsigned char* Ks, const unsigned char* Vs,
                                                       int kpitch, const _Float16* qbase, int64_t q_ts,
                                                       _Float16* obase, int64_t o_ts, int N, int D,
-                                                      float scale_log2e, int debug, int qt, int lane) {
+                                                      float scale_log2e, int debug, int qt, int lane,
+                                                      float* sqw = nullptr) {
     const int r = lane & 31, hh = lane >> 5;
     const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
     const int q = 32 * qt + r;
@@ -182,6 +188,38 @@ static __device__ __forceinline__ void attention_tile(const unsigned char* Ks, c
                 }
             }
         }
+    }
+    if constexpr (COLSQ) {
+        // The store's own packed halves, squared in fp32 and summed over the tile's 32 queries:
+        // a butterfly over lane bits 0 .. 4 (the half-lanes hold different columns and stay
+        // apart) — every lane ends with the same sum, added in an order that depends on nothing
+        // but the lane numbers.  Queries >= N contribute +0.  All 64 lanes take part (the
+        // exchanges sit outside the q < N branch).
+        typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
+        const bool liveq = q < N;
+        const bool store = obase != nullptr;
+        const float inv = 1.0f / l;
+        _Float16* orow = obase + (int64_t)q * o_ts;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int d = 32 * dt + 8 * g + 4 * hh;
+                uint2 w2;
+                w2.x = Vec<ECOFLAP_F16>::f2h_pk(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv);
+                w2.y = Vec<ECOFLAP_F16>::f2h_pk(o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
+                if (store && liveq && d < D) *(uint2*)(orow + d) = w2;
+                const h2_t a = __builtin_bit_cast(h2_t, w2.x), b = __builtin_bit_cast(h2_t, w2.y);
+                float v[4] = {(float)a[0], (float)a[1], (float)b[0], (float)b[1]};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = (liveq && d < D) ? v[j] * v[j] : 0.f;
+#pragma unroll
+                    for (int m_ = 1; m_ < 32; m_ <<= 1) v[j] += __shfl_xor(v[j], m_, 64);
+                }
+                if (r == 0) *(float4*)(sqw + d) = float4{v[0], v[1], v[2], v[3]};
+            }
+        return;
     }
     // lane (r, hh) holds O^T rows d = 32 dt + 8 g + 4 hh .. + 3 of its query: four halves per store
     if (q < N && !(debug & 16)) {

@@ -27,8 +27,9 @@ import yaml
 
 def build_parser():
     p = argparse.ArgumentParser(description="ECoFLaP pruning on MI355X (hot path only)")
-    p.add_argument("--shape", default="blip2", choices=["blip2", "t5", "vit"],
-                   help="blip2: EVA-ViT-g + Q-Former + FlanT5-XL; t5: FlanT5-XL; vit: ViT-B/16 CLIP shape")
+    p.add_argument("--shape", default="blip2", choices=["blip2", "t5", "vit", "clip"],
+                   help="blip2: EVA-ViT-g + Q-Former + FlanT5-XL; t5: FlanT5-XL; vit: ViT-B/16 CLIP shape; "
+                        "clip: OpenAI-CLIP ViT-B/16, both towers (CoOp's zero-shot trainer)")
     p.add_argument("--toy", action="store_true", help="CPU-sized shapes of the same families")
     p.add_argument("--device", default="cuda")
     # the reference's flags (names, types, defaults)
@@ -38,7 +39,11 @@ def build_parser():
     p.add_argument("--t5_prune_spec", type=str, default=None)
     p.add_argument("--vit_prune_spec", type=str, default=None)
     p.add_argument("--num_data", type=int, default=128)
-    p.add_argument("--prunining_dataset_batch_size", type=int, default=1)
+    p.add_argument("--prunining_dataset_batch_size", type=int, default=None,
+                   help="default 1; --shape clip: 16 (CoOp/trainers/zsclip.py:54)")
+    # CoOp/train.py's two spec flags (--shape clip)
+    p.add_argument("--visual_prune_spec", type=str, default=None)
+    p.add_argument("--language_prune_spec", type=str, default=None)
     p.add_argument("--is_global", action="store_true")
     p.add_argument("--sparsity_ratio_granularity", type=str, default=None)
     p.add_argument("--max_sparsity_per_layer", type=float, default=0.8)
@@ -82,7 +87,9 @@ def build_parser():
 
 def build_model_and_loader(args, device):
     from .shapes import synthetic as S
-    bs = args.prunining_dataset_batch_size
+    bs = args.prunining_dataset_batch_size or (16 if args.shape == "clip" else 1)
+    if args.shape == "clip":
+        return build_clip_model_and_loader(args, device, bs)
     if getattr(args, "unstaged", False):
         from .shapes.blip2_t5 import Blip2T5
         from .shapes.eva_clip import EVACLIP
@@ -113,6 +120,49 @@ def build_model_and_loader(args, device):
                                        num_classes=5 if args.toy else 1000, seed=args.seed,
                                        device=device)
     return model.eval(), loader
+
+
+CLIP_NUM_CLASSES = 100      # (a calibration batch pairs every image with the prompt of its own label)
+
+
+def build_clip_model_and_loader(args, device, bs):
+    """OpenAI-CLIP towers, `{"img", "label"}` calibration batches with distinct labels within a
+    batch (`shapes/clip_two_tower.py::clip_batches`), and a seeded prompt-id table in place of
+    CoOp's tokenised "a photo of a {class}." strings -> (model, loader); the closure the pruner
+    needs rides on the loader list as `.forward_to_cache`."""
+    from .pruners.losses import clip_contrastive
+    from .shapes.clip import clip_toy, clip_vit_b16
+    from .shapes.clip_two_tower import clip_batches
+    model = (clip_toy(fp16=False) if args.toy else clip_vit_b16(fp16=device.type != "cpu")).to(device)
+    context, vocab = model.context_length, model.vocab_size
+    classes = max(CLIP_NUM_CLASSES, bs)
+    g = torch.Generator().manual_seed(args.seed + 1)
+    prompts = torch.randint(1, vocab - 1, (classes, context), generator=g)
+    prompts[torch.arange(classes), torch.randint(1, context, (classes,), generator=g)] = vocab - 1   # end of text
+    loader = _ClipLoader(
+        {k: v.to(device) for k, v in b.items()}
+        for b in clip_batches(args.num_data, bs, img_size=32 if args.toy else 224, num_classes=classes,
+                              seed=args.seed))
+    loader.forward_to_cache = clip_contrastive(prompts.to(device))
+    return model.eval(), loader
+
+
+class _ClipLoader(list):
+    """The calibration batches, with the loss closure that belongs to their prompt table."""
+    forward_to_cache = None
+
+
+def clip_sparsity_json(sparsity_dict, out_dir):
+    """CoOp/trainers/zsclip.py:97-101: `sparsity_dict.json` in the output folder when stage 1 made
+    a table (indent 4) -> the path, or None."""
+    if sparsity_dict is None:
+        return None
+    import json
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "sparsity_dict.json")
+    with open(path, "w") as f:
+        json.dump(dict(sparsity_dict), f, indent=4)
+    return path
 
 
 def load_pruned_checkpoints(model, t5_pruned_checkpoint=None, vit_pruned_checkpoint=None):
@@ -185,6 +235,11 @@ def config_dict(args):
     if str(args.pruning_method).startswith("blipt5_"):
         cfg.update(t5_prune_spec=args.t5_prune_spec, vit_prune_spec=args.vit_prune_spec,
                    t5_pruning_method="none", vit_pruning_method="none")
+    elif str(args.pruning_method).startswith("clip_"):
+        # CoOp/train.py:76-82, :116-128 (PRUNER.PARAMS)
+        cfg.update(visual_prune_spec=args.visual_prune_spec, language_prune_spec=args.language_prune_spec,
+                   language_pruning_method="none", visual_pruning_method="none",
+                   language_model_prefix="transformer", visual_model_prefix="visual.transformer")
     elif str(args.pruning_method).startswith("t5_"):
         cfg.update(prune_spec=args.t5_prune_spec)
     else:
@@ -213,8 +268,12 @@ def main(argv=None, kernels=None):
     if kernels is not None:
         cfg["kernels"] = kernels
     pruner = load_pruner(args.pruning_method, model, loader, cfg=cfg)
+    if args.shape == "clip":
+        pruner.forward_to_cache = loader.forward_to_cache      # assigned from outside (zsclip.py:93)
     start = time.time()
     model, sparsity_dict = pruner.prune()
+    if args.shape == "clip":
+        clip_sparsity_json(sparsity_dict, args.out_dir)
     remaining = sum((p != 0).float().sum() for p in counted.parameters())
     print(float(remaining / orig_total * 100))
     if args.save_pruned_model:

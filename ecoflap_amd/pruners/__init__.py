@@ -14,3 +14,4 @@ from .sparsegpt import (  # noqa: F401,E402
 from .global_pruner import (  # noqa: F401,E402
     BLIPT5GlobalGradMagAbsPruner, BLIPT5GlobalMagPruner, BLIPT5GlobalMeZoPruner, BLIPT5GlobalPruner,
 )
+from .clip import CLIPLayerWandaPruner  # noqa: F401,E402

@@ -112,16 +112,26 @@ class _K6Collector:
         if any(p[0] is wrapped for p in self.pending):
             self.flush()           # a Linear called twice in one forward: in order, not at once
         if self.immediate:
-            self.pending.append((wrapped, x, batch, x._version))
+            self.pending.append((wrapped, x, batch, x._version, False))
             self.flush()
             return
-        self.pending.append((wrapped, x, batch, x._version))
+        self.pending.append((wrapped, x, batch, x._version, False))
+
+    def add_statistic(self, wrapped, sq, batch):
+        """raw mode: a site whose own statistic ||x_c||^2 of this forward is already reduced (the
+        attention kernel's epilogue, `ecoflap_mha_attention_colsq`): it takes that site's slot of
+        the sample's flat row as it stands — exactly what the K6 launch writes for the other
+        sites — and `merge()` replays it in global batch order with them."""
+        assert self.raw and sq.dim() == 1 and sq.dtype == torch.float32
+        if any(p[0] is wrapped for p in self.pending):
+            self.flush()
+        self.pending.append((wrapped, sq.view(1, -1), batch, sq._version, True))
 
     def flush(self):
         if not self.pending:
             return
         pend, self.pending = self.pending, []
-        stale = [w_ for w_, x, _, ver in pend if x._version != ver]
+        stale = [w_ for w_, x, _, ver, _st in pend if x._version != ver]
         if stale:
             raise RuntimeError(
                 f"{len(stale)} hooked Linear input(s) of this block were modified in place between "
@@ -129,28 +139,33 @@ class _K6Collector:
                 "statistic would read the overwritten values.  Construct the pruner with "
                 "k6_immediate=True (one launch per input, inside the hook, as the reference "
                 "reduces) for models that write their activations in place.")
-        pend = [(w_, x, b) for w_, x, b, _ in pend]
+        pend = [(w_, x, b, st) for w_, x, b, _, st in pend]
         if self.raw:
             # one forward may flush more than once (a Linear called twice): sites accumulate
             # until `end_sample`
             if self.flat is None or self._site_cursor + len(pend) > len(self.sites or []):
                 self._grow_sites(pend)
             items = []
-            for w_, x, b in pend:
+            for w_, x, b, st in pend:
                 w0, off, cols = self.sites[self._site_cursor]
                 assert w0 is w_ and cols == x.shape[1]
-                items.append((self.flat[off:off + cols], x, 0, None, b, True))
+                if st:      # reduced already: a device copy (recorded like a launch under capture)
+                    self.flat[off:off + cols].copy_(x.view(-1))
+                else:
+                    items.append((self.flat[off:off + cols], x, 0, None, b, True))
                 self.site_batches[self._site_cursor] = b
                 self._site_cursor += 1
                 if not self.capturing:
                     w_.nsamples += b
         else:
-            items = [(w_.scaler_row, x, w_.nsamples, w_.n_dev, b, False) for w_, x, b in pend]
-            for w_, _, b in pend:
+            items = [(w_.scaler_row, x, w_.nsamples, w_.n_dev, b, False) for w_, x, b, _ in pend]
+            for w_, _, b, _ in pend:
                 if w_.n_dev is None:
                     w_.nsamples += b
                 else:
                     w_.dev_batch = b
+        if not items:
+            return
         self.kernels.colsqnorm_accum_multi(items, self.ws)
         self.launches += 1
         self._flushes.append(items)
@@ -161,7 +176,7 @@ class _K6Collector:
         assert not self.samples, "hook sequence changed between calibration samples"
         sites = list(self.sites or [])
         off = sum(c for _, _, c in sites)
-        for w_, x, _ in pend:
+        for w_, x, _, _ in pend:
             sites.append((w_, off, x.shape[1]))
             off += x.shape[1]
         old = self.flat

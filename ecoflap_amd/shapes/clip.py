@@ -13,7 +13,15 @@ output read in place, causal in the text tower), and the patch embedding is one 
 (`fused.patches_gemm`, no MIOpen: DESIGN §5).  Where the kernel refuses a shape (head width other
 than 64, more than 224 tokens) the block stays on `nn.MultiheadAttention`.
 
-Not here yet: `stage_plan()` and the `clip_wanda_pruner` family."""
+`clip_wanda_pruner` (pruners/clip.py) prunes these towers.  While its stage 2 hooks a block, the
+block reports the operands of the two attention projections, which no `nn.Linear` hook can see
+(`_stat_sink`, off by default: `attention()` then is the code above, unchanged): `ln_1(x)` for the
+in-projection, and for the out-projection the output of the reference's UNMASKED side copy of the
+attention (CoOp/trainers/pruners/wanda_pruner.py:300-322) — on the GPU in fp16 as the column
+statistic `fused.mha_attention_colsq` leaves (in the visual tower the same kernel call that
+produces the block's output), everywhere else as the reference's literal op chain in torch.
+
+Not here yet: `stage_plan()`."""
 import math
 from collections import OrderedDict
 
@@ -75,7 +83,56 @@ class ResidualAttentionBlock(nn.Module):
         y = fused.mha_attention(qkv, a.num_heads, a.head_dim ** -0.5, causal=causal, seq_first=True)
         return None if y is None else a.out_proj(y)
 
+    # stage 2 of `clip_wanda_pruner` sets this on the block it hooks (pruners/clip.py::_AttentionSites)
+    _stat_sink = None
+
+    def _side_attention(self, x):
+        """The reference's `hacky_attn` up to its `proj` (wanda_pruner.py:69-101 with this block's
+        in-projection as `qkv`, :302-306): no mask in either tower, `q * scale` before the
+        product, every op in the activation's dtype.  [L, N, D] -> `proj`'s input [N, L, D]."""
+        a = self.attn
+        x = x.permute(1, 0, 2)
+        B, N, C = x.shape
+        qkv = F.linear(x, a.in_proj_weight, a.in_proj_bias)
+        qkv = qkv.reshape(B, N, 3, a.num_heads, -1).permute(2, 0, 3, 1, 4)
+        q, k, v = qkv[0], qkv[1], qkv[2]
+        q = q * (a.head_dim ** -0.5)
+        attn = (q @ k.transpose(-2, -1)).softmax(dim=-1)
+        return (attn @ v).transpose(1, 2).reshape(B, N, -1)
+
+    def _reporting_attention(self, x, sink):
+        """`attention(x)` of a hooked block: the same result, and both projections' operands (or
+        the out-projection's finished statistic) handed to `sink`."""
+        a = self.attn
+        sink.operand("attn.in_proj", x.permute(1, 0, 2))
+        fused_ok = not (torch.is_grad_enabled() or x.device.type != "cuda" or x.dtype != torch.float16
+                        or x.dim() != 3 or a.in_proj_weight is None
+                        or a.in_proj_weight.dtype != torch.float16)
+        causal = self._mask_is_causal(x.shape[0]) if fused_ok else None
+        if causal is not None and sink.takes_statistic():
+            from . import fused
+            qkv = F.linear(x, a.in_proj_weight, a.in_proj_bias)         # [L, N, 3D]
+            scale = a.head_dim ** -0.5
+            if causal:      # the forward is masked, the statistic is not: a second, store-free pass
+                y = fused.mha_attention(qkv, a.num_heads, scale, causal=True, seq_first=True)
+                res = None if y is None else fused.mha_attention_colsq(qkv, a.num_heads, scale, out=False,
+                                                                      seq_first=True)
+            else:
+                res = fused.mha_attention_colsq(qkv, a.num_heads, scale, out=True, seq_first=True)
+                y = None if res is None else res[0]
+            if res is not None:
+                sink.statistic("attn.out_proj", res[1], x.shape[1])
+                return a.out_proj(y)
+        sink.operand("attn.out_proj", self._side_attention(x))
+        return self._plain_attention(x)
+
     def attention(self, x):
+        sink = self._stat_sink
+        if sink is not None:
+            return self._reporting_attention(x, sink)
+        return self._plain_attention(x)
+
+    def _plain_attention(self, x):
         y = self._fused_attention(x)
         if y is not None:
             return y

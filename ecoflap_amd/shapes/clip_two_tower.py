@@ -2,8 +2,8 @@
 is the contract: `model(image, text) -> (logits_per_image, logits_per_text)` = `logit_scale.exp()`
 times the cosine similarities of the normalised image and text features, logit_scale initialised
 to log(1/0.07), :291).  Toy MLP towers for the closure's tests; the OpenAI-CLIP ViT towers
-themselves are `shapes/clip.py`.  CoOp's BPE tokenizer is outside the hot path and the
-`clip_*_pruner` family is not built yet (DESIGN.md \u00a78)."""
+themselves are `shapes/clip.py`.  CoOp's BPE tokenizer is outside the hot path; the
+pruner of this family is `clip_wanda_pruner` (pruners/clip.py)."""
 import math
 
 import torch

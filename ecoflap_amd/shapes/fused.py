@@ -38,6 +38,10 @@ def _get():
         lib.ecoflap_vit_attention.argtypes = [vp, vp, i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_vit_attention_v1.argtypes = [vp, vp, i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_mha_attention.argtypes = [vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, ci, f32, ci, vp]
+        lib.ecoflap_mha_attention_colsq_workspace_bytes.restype = ctypes.c_size_t
+        lib.ecoflap_mha_attention_colsq_workspace_bytes.argtypes = [i64, i64]
+        lib.ecoflap_mha_attention_colsq.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, i64, i64, i64, i64,
+                                                    i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_multi_copy.argtypes = [vp, ci, vp]
         lib.ecoflap_multi_compare.argtypes = [vp, ci, vp, vp]
         _lib = lib
@@ -223,6 +227,43 @@ def mha_attention(qkv, heads, scale, causal=False, seq_first=True):
     if rc != 0:
         raise _hip.EcoflapHipError(f"ecoflap_mha_attention failed ({rc})")
     return out
+
+
+def mha_attention_colsq(qkv, heads, scale, out=True, seq_first=True):
+    """The NON-causal `mha_attention` of `qkv` together with the Wanda column statistic of its
+    output: sq[c] = sum over all batch * tokens rows of float(f16 output[row, c]) ** 2, fp32
+    [heads * 64] — `torch.norm(o.reshape(-1, D).t().float(), p=2, dim=1) ** 2` without reading the
+    output back (`ecoflap_mha_attention_colsq`, csrc/mha_attention.hip; no atomics: bitwise
+    repeatable).  out=True: the merged heads are written too, with `mha_attention(causal=False)`'s
+    bits; out=False: they are never stored (the statistic of a tower whose real forward is masked).
+    Launches only, and its buffers come from torch's allocator: usable inside a graph capture.
+    -> (output or None, sq), or None where `mha_attention` would return None."""
+    import os
+    if (torch.is_grad_enabled() or qkv.device.type != "cuda" or qkv.dtype != torch.float16
+            or qkv.dim() != 3 or qkv.stride(2) != 1 or os.environ.get("ECOFLAP_NO_FUSED_ATTENTION")):
+        return None
+    if heads < 1 or qkv.shape[2] != 3 * heads * 64 or not (0.0 < float(scale) < float("inf")):
+        return None
+    t_dim, b_dim = (0, 1) if seq_first else (1, 0)
+    L, B = qkv.shape[t_dim], qkv.shape[b_dim]
+    if not (1 <= L <= 224) or B < 1:
+        return None
+    lib = _get()
+    y = (torch.empty(qkv.shape[0], qkv.shape[1], heads * 64, dtype=qkv.dtype, device=qkv.device)
+         if out else None)
+    sq = torch.empty(heads * 64, dtype=torch.float32, device=qkv.device)
+    nb = int(lib.ecoflap_mha_attention_colsq_workspace_bytes(B, heads))
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=qkv.device)
+    rc = lib.ecoflap_mha_attention_colsq(
+        qkv.data_ptr(), None if y is None else y.data_ptr(), sq.data_ptr(), ws.data_ptr(), ws.numel(),
+        B, L, heads, 64, qkv.stride(t_dim), qkv.stride(b_dim),
+        0 if y is None else y.stride(t_dim), 0 if y is None else y.stride(b_dim), float(scale),
+        _hip.DTYPE_CODE[qkv.dtype], _stream())
+    if rc in (-3, -5):      # ECOFLAP_ESIZE / ECOFLAP_EALIGN: a view the kernel cannot address in place
+        return None
+    if rc != 0:
+        raise _hip.EcoflapHipError(f"ecoflap_mha_attention_colsq failed ({rc})")
+    return y, sq
 
 
 class _CopyItem(ctypes.Structure):

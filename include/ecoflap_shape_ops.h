@@ -92,6 +92,29 @@ int ecoflap_mha_attention(const void* qkv, void* out, int64_t batch, int64_t tok
                           int64_t out_token_stride, int64_t out_batch_stride, int causal,
                           float scale, int dtype, void* stream);
 
+/* The NON-causal ecoflap_mha_attention with the Wanda column statistic of its output as an epilogue
+ * (CoOp/trainers/pruners/wanda_pruner.py:69-104 + :159-172 + :311-313 + :334-341: the side copy
+ * `hacky_attn` of a CLIP block, which has no mask in either tower, hooked at its `proj`, whose
+ * input goes through WrappedGPT's `torch.norm(inp.float(), p=2, dim=1) ** 2`):
+ *   sq[h * 64 + d] = sum over all batch * tokens rows of (float)(f16-rounded out[row, h, d])^2
+ * sq: [heads * 64] fp32 on the device, overwritten.  out MAY be null: the output is then never
+ * stored (the text tower, whose real forward is causal: the unmasked output exists only to be
+ * reduced); given, it receives the bits ecoflap_mha_attention(causal = 0) writes (the out strides
+ * are ignored when out is null).  workspace: caller-owned, at least
+ * ecoflap_mha_attention_colsq_workspace_bytes(batch, heads) bytes, 16-byte aligned, overwritten; it
+ * needs no initialisation and carries nothing between calls.  No atomics: per-wave, per-workgroup
+ * and per-sample partial sums are added in an order fixed by the shape, so sq is bitwise
+ * repeatable and does not depend on the launch schedule; query rows >= tokens contribute nothing.
+ * Launches only (no synchronisation, no allocation): usable inside a captured graph.  Shape limits
+ * and error codes of ecoflap_mha_attention; a short workspace is ECOFLAP_ESIZE.  Nothing is launched
+ * on an error. */
+size_t ecoflap_mha_attention_colsq_workspace_bytes(int64_t batch, int64_t heads);
+int ecoflap_mha_attention_colsq(const void* qkv, void* out, float* sq, void* workspace,
+                                size_t workspace_bytes, int64_t batch, int64_t tokens, int64_t heads,
+                                int64_t head_dim, int64_t qkv_token_stride, int64_t qkv_batch_stride,
+                                int64_t out_token_stride, int64_t out_batch_stride, float scale,
+                                int dtype, void* stream);
+
 /* Up to ECOFLAP_COPY_MAX_ITEMS device-to-device copies (non-overlapping, any alignment) in
  * one launch: the loop's state hand-overs between static graph buffers. */
 #define ECOFLAP_COPY_MAX_ITEMS 32
