@@ -20,6 +20,11 @@
 //     live in two registers per lane, Hinv1 sits in LDS, each of the `count` sequential steps
 //     is a lane broadcast + a fully rounded fp32 divide + one multiply and one subtract per
 //     lane (two roundings, as torch's outer-product-then-subtract; no fma contraction).
+//
+// The trailing update W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:] (:216) is `ecoflap_sparsegpt_trailing`
+// below, an fp32 MFMA kernel of this file, and `ecoflap_sparsegpt_matrix` queues the whole column
+// sweep of one Linear — widen, every block step, every trailing update, round back — from one
+// host call (CoOp/trainers/pruners/sparsegpt_pruner.py:176-189, :261-307).
 #include "common.h"
 
 struct SgptSelState {
@@ -215,18 +220,26 @@ extern "C" size_t ecoflap_sparsegpt_workspace_bytes(void) { return sizeof(SgptSe
 // factor of the inverse Hessian; block columns [i1, i1+count); k = int(rows*count*sparsity).
 // mask_in (optional): uint8[rows*count] mask to use instead of the threshold (not used by the
 // reference's unstructured path).  err_out: float[rows*count]; mask_out (optional).
-extern "C" int ecoflap_sparsegpt_block(float* W, int64_t rows, int64_t ldw, const float* Hinv,
-                                       int64_t ldh, int64_t i1, int count, int64_t k,
-                                       const uint8_t* mask_in, float* err_out, uint8_t* mask_out,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
+// argument checks of the block step (no HIP call is made before they pass)
+static int sgpt_block_check(int64_t rows, int64_t ldw, int64_t ldh, int64_t i1, int count, int64_t k,
+                            bool thresholded) {
     if (rows <= 0 || count <= 0 || count > 128 || ldw < i1 + count || ldh < i1 + count || i1 < 0)
         return ECOFLAP_ESIZE;
     const int64_t n = rows * count;
-    if (!mask_in && (k < 0 || k >= n || n >= (int64_t)0xffffffffLL)) return ECOFLAP_ESIZE;
-    if (!W || !Hinv || !err_out || !workspace) return ECOFLAP_ENULL;
-    if (workspace_bytes < sizeof(SgptSelState)) return ECOFLAP_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    SgptSelState* st = (SgptSelState*)workspace;
+    if (thresholded && (k < 0 || k >= n || n >= (int64_t)0xffffffffLL)) return ECOFLAP_ESIZE;
+    return 0;
+}
+
+static int sgpt_nm_check(int count, int n, int m) {
+    if (n <= 0 || m < n || m > 16 || (count % m != 0 && count % m < n)) return ECOFLAP_ESIZE;
+    return 0;
+}
+
+// the launches of one thresholded (or given-mask) block step; arguments already checked
+static int sgpt_block_launch(float* W, int64_t rows, int64_t ldw, const float* Hinv, int64_t ldh,
+                             int64_t i1, int count, int64_t k, const uint8_t* mask_in, float* err_out,
+                             uint8_t* mask_out, SgptSelState* st, hipStream_t s) {
+    const int64_t n = rows * count;
     const uint32_t rank0 = (uint32_t)(k + 1);
     if (!mask_in) {
         hipError_t e = hipMemsetAsync(st, 0, sizeof(SgptSelState), s);
@@ -248,20 +261,295 @@ extern "C" int ecoflap_sparsegpt_block(float* W, int64_t rows, int64_t ldw, cons
     return 0;
 }
 
+static int sgpt_block_nm_launch(float* W, int64_t rows, int64_t ldw, const float* Hinv, int64_t ldh,
+                                int64_t i1, int count, int n, int m, float* err_out, uint8_t* mask_out,
+                                hipStream_t s) {
+    const size_t lds = ((size_t)count * (count + 1) / 2) * sizeof(float);
+    hipLaunchKernelGGL(sgpt_sweep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), lds, s, W, rows,
+                       ldw, Hinv, ldh, i1, count, 0u, (const SgptSelState*)nullptr, 0,
+                       (const uint8_t*)nullptr, err_out, mask_out, n, m);
+    ECO_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ecoflap_sparsegpt_block(float* W, int64_t rows, int64_t ldw, const float* Hinv,
+                                       int64_t ldh, int64_t i1, int count, int64_t k,
+                                       const uint8_t* mask_in, float* err_out, uint8_t* mask_out,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = sgpt_block_check(rows, ldw, ldh, i1, count, k, !mask_in);
+    if (rc) return rc;
+    if (!W || !Hinv || !err_out || !workspace) return ECOFLAP_ENULL;
+    if (workspace_bytes < sizeof(SgptSelState)) return ECOFLAP_EWORKSPACE;
+    return sgpt_block_launch(W, rows, ldw, Hinv, ldh, i1, count, k, mask_in, err_out, mask_out,
+                             (SgptSelState*)workspace, (hipStream_t)stream);
+}
+
 // The same block step under n:m (sparsegpt_pruner.py:190, :196-198; dead in the reference's shipped
 // configs): no threshold, the mask grows during the sweep.  0 < n <= m <= 16; a group cut short by
 // the block's end must hold at least n columns (the reference's topk raises otherwise).
 extern "C" int ecoflap_sparsegpt_block_nm(float* W, int64_t rows, int64_t ldw, const float* Hinv,
                                           int64_t ldh, int64_t i1, int count, int n, int m,
                                           float* err_out, uint8_t* mask_out, void* stream) {
-    if (rows <= 0 || count <= 0 || count > 128 || ldw < i1 + count || ldh < i1 + count || i1 < 0)
-        return ECOFLAP_ESIZE;
-    if (n <= 0 || m < n || m > 16 || (count % m != 0 && count % m < n)) return ECOFLAP_ESIZE;
+    int rc = sgpt_block_check(rows, ldw, ldh, i1, count, 0, false);
+    if (rc) return rc;
+    if ((rc = sgpt_nm_check(count, n, m)) != 0) return rc;
     if (!W || !Hinv || !err_out) return ECOFLAP_ENULL;
-    const size_t lds = ((size_t)count * (count + 1) / 2) * sizeof(float);
-    hipLaunchKernelGGL(sgpt_sweep_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), lds,
-                       (hipStream_t)stream, W, rows, ldw, Hinv, ldh, i1, count, 0u,
-                       (const SgptSelState*)nullptr, 0, (const uint8_t*)nullptr, err_out, mask_out, n, m);
+    return sgpt_block_nm_launch(W, rows, ldw, Hinv, ldh, i1, count, n, m, err_out, mask_out,
+                                (hipStream_t)stream);
+}
+
+// ---- trailing update: W[:, j0:cols] -= Err[rows, count] @ Hinv[i1:i1+count, j0:cols] -------------
+// (sparsegpt_pruner.py:302 of the CoOp tree, :216 of the LAVIS one) on v_mfma_f32_32x32x2_f32, in
+// the tiling of csrc/gemm_f32.hip: a 64 x 64 tile of W per 256-thread workgroup, one 32 x 32 MFMA
+// tile per wave, k in chunks of 32 through LDS.  `count` is at most 128, so a tile is at most four
+// chunks: they go through ONE pair of LDS images with two barriers each; the next chunk's global
+// loads are issued into registers before this chunk multiplies, and the lane's 16 elements of W are
+// fetched before the first chunk, so a workgroup waits for memory once, not once per chunk (the
+// update of a CLIP matrix is latency bound: 0.6 GFLOP at most).
+//
+// Numerics: every output element is ONE fp32 accumulation chain from +0 over k in a FIXED order —
+// ascending quads, inside quad q the MFMA steps take the pairs (4q, 4q + 2) then (4q + 1, 4q + 3),
+// one rounding per accumulate — followed by one subtraction from W.  k slots past `count` hold
+// 0 x 0.  No atomics, no split over k: the same call gives the same bits, whatever the grid.
+//
+// LDS: Err rows at a pitch of 34 floats (the 8-byte k-pair reads of a half-wave fall on 32
+// distinct even banks, as GF_LDK); Hinv rows as they lie, 64 columns wide (a half-wave reads 32
+// consecutive floats of one k row: conflict free).  Every global access is bounds checked: rows
+// past `rows`, columns past `cols` and k past `count` read as zero and are never stored.
+typedef float sg_f32x16 __attribute__((ext_vector_type(16)));
+typedef float sg_f32x2 __attribute__((ext_vector_type(2)));
+
+#define SGT_BT 64               // tile edge
+#define SGT_BK 32               // k per chunk
+#define SGT_LDA (SGT_BK + 2)
+
+__global__ __launch_bounds__(256) void sgpt_trailing_kernel(float* __restrict__ W, int64_t rows,
+                                                            int64_t cols, int64_t ldw,
+                                                            const float* __restrict__ Err,
+                                                            const float* __restrict__ Hinv, int64_t ldh,
+                                                            int64_t i1, int count, int64_t j0,
+                                                            int tiles_n) {
+    __shared__ __attribute__((aligned(16))) float As[SGT_BT * SGT_LDA];      // Err  [row][k]
+    __shared__ __attribute__((aligned(16))) float Bs[SGT_BK * SGT_BT];       // Hinv [k][col]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tn = blockIdx.x % tiles_n, tm = blockIdx.x / tiles_n;
+    const int64_t m0 = (int64_t)tm * SGT_BT, n0 = j0 + (int64_t)tn * SGT_BT;
+    const int wy = wave >> 1, wx = wave & 1;
+    const int r32 = lane & 31, kh = lane >> 5;
+    sg_f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    // the tile of W this lane will update is on its way before anything else (C/D map of the
+    // 32 x 32 shapes: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5))
+    const int64_t col = n0 + 32 * wx + r32;
+    float wv[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int64_t row = m0 + 32 * wy + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        wv[r] = (row < rows && col < cols) ? W[row * ldw + col] : 0.f;
+    }
+    const int ak = tid & 31, ar = tid >> 5;         // Err: k ak of rows ar + 8 i
+    const int bc = tid & 63, bk = tid >> 6;         // Hinv: column bc of k rows bk + 4 i
+    float pa[8], pb[8];
+    auto load_chunk = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int64_t row = m0 + ar + 8 * i;
+            const int k = k0 + ak;
+            pa[i] = (row < rows && k < count) ? Err[row * count + k] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int k = k0 + bk + 4 * i;
+            const int64_t c = n0 + bc;
+            pb[i] = (k < count && c < cols) ? Hinv[(i1 + k) * ldh + c] : 0.f;
+        }
+    };
+    load_chunk(0);
+    for (int k0 = 0; k0 < count; k0 += SGT_BK) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            As[(ar + 8 * i) * SGT_LDA + ak] = pa[i];
+            Bs[(bk + 4 * i) * SGT_BT + bc] = pb[i];
+        }
+        __syncthreads();
+        if (k0 + SGT_BK < count) load_chunk(k0 + SGT_BK);      // on its way while this chunk multiplies
+        const float* A = &As[(32 * wy + r32) * SGT_LDA + 2 * kh];
+        const float* B = &Bs[(2 * kh) * SGT_BT + 32 * wx + r32];
+#pragma unroll
+        for (int q = 0; q < SGT_BK / 4; ++q) {
+            const sg_f32x2 av = *(const sg_f32x2*)(A + 4 * q);
+            const float b0 = B[(4 * q) * SGT_BT], b1 = B[(4 * q + 1) * SGT_BT];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0], b0, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1], b1, acc, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    if (col >= cols) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int64_t row = m0 + 32 * wy + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        if (row < rows) W[row * ldw + col] = wv[r] - acc[r];
+    }
+}
+
+static int sgpt_trailing_check(int64_t rows, int64_t cols, int64_t ldw, int64_t ldh, int64_t i1,
+                               int count, int64_t j0) {
+    if (rows <= 0 || count <= 0 || count > 128 || i1 < 0 || j0 < 0 || cols < j0 || ldw < cols ||
+        ldh < cols)
+        return ECOFLAP_ESIZE;
+    const int64_t tiles = ((rows + SGT_BT - 1) / SGT_BT) * ((cols - j0 + SGT_BT - 1) / SGT_BT);
+    if (tiles > 0x7fffffffLL) return ECOFLAP_ESIZE;
+    return 0;
+}
+
+static int sgpt_trailing_launch(float* W, int64_t rows, int64_t cols, int64_t ldw, const float* Err,
+                                const float* Hinv, int64_t ldh, int64_t i1, int count, int64_t j0,
+                                hipStream_t s) {
+    if (cols == j0) return 0;
+    const int64_t tiles_n = (cols - j0 + SGT_BT - 1) / SGT_BT;
+    const int64_t tiles = ((rows + SGT_BT - 1) / SGT_BT) * tiles_n;
+    hipLaunchKernelGGL(sgpt_trailing_kernel, dim3((unsigned)tiles), dim3(256), 0, s, W, rows, cols, ldw,
+                       Err, Hinv, ldh, i1, count, j0, (int)tiles_n);
     ECO_CHECK_LAUNCH();
     return 0;
+}
+
+// W: float[rows, ldw]; Err: float[rows, count] as the block step leaves it (pitch `count`); Hinv:
+// float[*, ldh], its rows [i1, i1 + count) and columns [j0, cols) are read.
+extern "C" int ecoflap_sparsegpt_trailing(float* W, int64_t rows, int64_t cols, int64_t ldw,
+                                          const float* Err, const float* Hinv, int64_t ldh,
+                                          int64_t i1, int count, int64_t j0, void* stream) {
+    const int rc = sgpt_trailing_check(rows, cols, ldw, ldh, i1, count, j0);
+    if (rc) return rc;
+    if (!W || !Err || !Hinv) return ECOFLAP_ENULL;
+    return sgpt_trailing_launch(W, rows, cols, ldw, Err, Hinv, ldh, i1, count, j0, (hipStream_t)stream);
+}
+
+// ---- the whole sweep of one Linear from one host call ------------------------------------------
+// widen: W32 = float(w), dead columns zeroed (`W = W.float(); W[:, dead] = 0`); narrow: w =
+// W32.to(dtype), round to nearest even as torch's cast (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32).
+// VEC: one 16-byte vector of the storage dtype per thread (cols a multiple of its width, so a
+// vector never straddles a row and the dead mask is read at `e % cols`); otherwise one element.
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void sgpt_widen_kernel(const void* __restrict__ w, float* __restrict__ W32,
+                                                         int64_t n, int64_t cols,
+                                                         const uint8_t* __restrict__ dead) {
+    typedef Vec<DT> V;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        if (t * V::N >= n) return;
+        float f[V::N];
+        V::unpack(ld16(w, t), f);
+        if (dead) {
+            const int64_t c0 = (t * V::N) % cols;
+#pragma unroll
+            for (int i = 0; i < V::N; ++i)
+                if (dead[c0 + i]) f[i] = 0.f;
+        }
+#pragma unroll
+        for (int v = 0; v < V::N / 4; ++v) st16(W32, t * (V::N / 4) + v, Vec<ECOFLAP_F32>::pack(f + 4 * v));
+    } else {
+        if (t >= n) return;
+        const float x = V::load1(w, t);
+        W32[t] = (dead && dead[t % cols]) ? 0.f : x;
+    }
+}
+
+template <int DT, bool VEC>
+__global__ __launch_bounds__(256) void sgpt_narrow_kernel(const float* __restrict__ W32, void* __restrict__ w,
+                                                          int64_t n) {
+    typedef Vec<DT> V;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        if (t * V::N >= n) return;
+        float f[V::N];
+#pragma unroll
+        for (int v = 0; v < V::N / 4; ++v) Vec<ECOFLAP_F32>::unpack(ld16(W32, t * (V::N / 4) + v), f + 4 * v);
+        st16(w, t, V::pack(f));
+    } else {
+        if (t >= n) return;
+        V::store1(w, t, W32[t]);
+    }
+}
+
+template <int DT>
+static void sgpt_convert_launch(bool widen, void* w, float* W32, int64_t rows, int64_t cols,
+                                const uint8_t* dead, hipStream_t s) {
+    const int64_t n = rows * cols;
+    const bool vec = cols % Vec<DT>::N == 0 && aligned16(w) && aligned16(W32);
+    const int64_t threads = vec ? n / Vec<DT>::N : n;
+    const dim3 grid((unsigned)((threads + 255) / 256)), blk(256);
+    if (widen) {
+        if (vec) hipLaunchKernelGGL((sgpt_widen_kernel<DT, true>), grid, blk, 0, s, w, W32, n, cols, dead);
+        else hipLaunchKernelGGL((sgpt_widen_kernel<DT, false>), grid, blk, 0, s, w, W32, n, cols, dead);
+    } else {
+        if (vec) hipLaunchKernelGGL((sgpt_narrow_kernel<DT, true>), grid, blk, 0, s, W32, w, n);
+        else hipLaunchKernelGGL((sgpt_narrow_kernel<DT, false>), grid, blk, 0, s, W32, w, n);
+    }
+}
+
+static int sgpt_convert(bool widen, int dtype, void* w, float* W32, int64_t rows, int64_t cols,
+                        const uint8_t* dead, hipStream_t s) {
+    if (dtype == ECOFLAP_F32) sgpt_convert_launch<ECOFLAP_F32>(widen, w, W32, rows, cols, dead, s);
+    else if (dtype == ECOFLAP_F16) sgpt_convert_launch<ECOFLAP_F16>(widen, w, W32, rows, cols, dead, s);
+    else sgpt_convert_launch<ECOFLAP_BF16>(widen, w, W32, rows, cols, dead, s);
+    ECO_CHECK_LAUNCH();
+    return 0;
+}
+
+static inline size_t sg_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// workspace of `ecoflap_sparsegpt_matrix`: the fp32 working copy [rows, cols], Err [rows, 128] and
+// the selection state, each on a 256-byte boundary (0 for sizes the entry refuses)
+extern "C" size_t ecoflap_sparsegpt_matrix_workspace_bytes(int64_t rows, int64_t cols) {
+    if (rows <= 0 || cols <= 0 || rows > ((int64_t)1 << 40) / cols) return 0;
+    return sg_align256((size_t)rows * (size_t)cols * 4) + sg_align256((size_t)rows * 128 * 4) +
+           sg_align256(sizeof(SgptSelState));
+}
+
+// SparseGPT.fasterprune after the factorisation, for one Linear w[rows, cols] (contiguous, storage
+// dtype, read and written in place): W = w.float(); W[:, dead] = 0; per block of `blocksize` columns
+// the block step at rank ranks_host[block] = int(rows * count * sparsity) (a HOST array, read before
+// this call returns; unused under n:m) or the n:m step, then the trailing update where columns
+// remain; w = W.to(dtype).  Everything is queued on `stream`; nothing waits for the device.
+extern "C" int ecoflap_sparsegpt_matrix(void* w, int dtype, int64_t rows, int64_t cols,
+                                        const float* Hinv, int64_t ldh, const uint8_t* dead,
+                                        int blocksize, const int64_t* ranks_host, int prune_n,
+                                        int prune_m, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
+    if (!dtype_ok(dtype)) return ECOFLAP_EDTYPE;
+    if (rows <= 0 || cols <= 0 || blocksize <= 0 || blocksize > 128 || ldh < cols ||
+        rows > ((int64_t)1 << 40) / cols)
+        return ECOFLAP_ESIZE;
+    if (!w || !Hinv || !workspace || (prune_n == 0 && !ranks_host)) return ECOFLAP_ENULL;
+    if (prune_n < 0 || (prune_n == 0 && prune_m != 0)) return ECOFLAP_ESIZE;
+    for (int64_t i1 = 0, b = 0; i1 < cols; i1 += blocksize, ++b) {
+        const int count = (int)(cols - i1 < blocksize ? cols - i1 : blocksize);
+        int rc = sgpt_block_check(rows, cols, ldh, i1, count, prune_n ? 0 : ranks_host[b], prune_n == 0);
+        if (rc == 0 && prune_n) rc = sgpt_nm_check(count, prune_n, prune_m);
+        if (rc == 0 && i1 + count < cols) rc = sgpt_trailing_check(rows, cols, cols, ldh, i1, count, i1 + count);
+        if (rc) return rc;
+    }
+    if (workspace_bytes < ecoflap_sparsegpt_matrix_workspace_bytes(rows, cols)) return ECOFLAP_EWORKSPACE;
+    if (!aligned16(workspace)) return ECOFLAP_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    float* W32 = (float*)workspace;
+    float* Err = (float*)((char*)workspace + sg_align256((size_t)rows * (size_t)cols * 4));
+    SgptSelState* st = (SgptSelState*)((char*)Err + sg_align256((size_t)rows * 128 * 4));
+    int rc = sgpt_convert(true, dtype, w, W32, rows, cols, dead, s);
+    if (rc) return rc;
+    for (int64_t i1 = 0, b = 0; i1 < cols; i1 += blocksize, ++b) {
+        const int count = (int)(cols - i1 < blocksize ? cols - i1 : blocksize);
+        if (prune_n)
+            rc = sgpt_block_nm_launch(W32, rows, cols, Hinv, ldh, i1, count, prune_n, prune_m, Err, nullptr, s);
+        else
+            rc = sgpt_block_launch(W32, rows, cols, Hinv, ldh, i1, count, ranks_host[b], nullptr, Err, nullptr, st, s);
+        if (rc) return rc;
+        if (i1 + count < cols) {
+            rc = sgpt_trailing_launch(W32, rows, cols, cols, Err, Hinv, ldh, i1, count, i1 + count, s);
+            if (rc) return rc;
+        }
+    }
+    return sgpt_convert(false, dtype, w, W32, rows, cols, nullptr, s);
 }

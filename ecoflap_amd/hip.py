@@ -34,6 +34,7 @@ EXPORTS = [
     "ecoflap_wanda_prune_block", "ecoflap_wanda_fallback_counts",
     "ecoflap_mask_mul", "ecoflap_allocate_sparsity",
     "ecoflap_sparsegpt_workspace_bytes", "ecoflap_sparsegpt_block", "ecoflap_sparsegpt_block_nm",
+    "ecoflap_sparsegpt_trailing", "ecoflap_sparsegpt_matrix_workspace_bytes", "ecoflap_sparsegpt_matrix",
     "ecoflap_hessian_workspace_bytes", "ecoflap_hessian_accum", "ecoflap_cholesky_workspace_bytes", "ecoflap_cholesky_f32",
     "ecoflap_cholesky_inverse_workspace_bytes", "ecoflap_cholesky_inverse_f32",
     "ecoflap_grad_accum_multi", "ecoflap_global_prune_workspace_bytes",
@@ -156,6 +157,10 @@ def load_library():
     lib.ecoflap_cholesky_inverse_f32.argtypes = [vp, i64, i64, vp, i64, vp, sz, vp]
     lib.ecoflap_sparsegpt_block.argtypes = [vp, i64, i64, vp, i64, i64, ci, i64, vp, vp, vp, vp, sz, vp]
     lib.ecoflap_sparsegpt_block_nm.argtypes = [vp, i64, i64, vp, i64, i64, ci, ci, ci, vp, vp, vp]
+    lib.ecoflap_sparsegpt_trailing.argtypes = [vp, i64, i64, i64, vp, vp, i64, i64, ci, i64, vp]
+    lib.ecoflap_sparsegpt_matrix_workspace_bytes.restype = sz
+    lib.ecoflap_sparsegpt_matrix_workspace_bytes.argtypes = [i64, i64]
+    lib.ecoflap_sparsegpt_matrix.argtypes = [vp, ci, i64, i64, vp, i64, vp, ci, vp, ci, ci, vp, sz, vp]
     lib.ecoflap_hessian_workspace_bytes.restype = sz
     lib.ecoflap_hessian_workspace_bytes.argtypes = [i64, i64]
     lib.ecoflap_hessian_accum.argtypes = [vp, vp, i64, i64, ci, i64, i64, vp, sz, vp]
@@ -221,6 +226,7 @@ class HipKernels:
         self.k6_ws = Workspace(zeroed=True)
         self.k6_multi_ws = Workspace(zeroed=True)     # its own layout: never shared with k6_ws
         self.hess_ws = Workspace()
+        self.sgpt_ws = Workspace()                    # a Linear's fp32 working copy: kept apart from `ws`
         self._pair_tables = {}
 
     PAIR_TABLES_KEPT = 8      # >= the first-order loop's lanes (default 3), each with its own buffers
@@ -805,6 +811,45 @@ class HipKernels:
         _check(self.lib.ecoflap_sparsegpt_block_nm(
             _ptr(W), W.shape[0], W.stride(0), _ptr(Hinv), Hinv.stride(0), int(i1), int(count),
             int(n), int(m), _ptr(err_out), _ptr(mask_out), _stream()), "ecoflap_sparsegpt_block_nm")
+
+    def sparsegpt_trailing(self, W, err, Hinv, i1, count, j0):
+        """W[:, j0:] -= err[rows, count] @ Hinv[i1:i1+count, j0:] on the fp32 working copy (the
+        trailing update of a block step, csrc/sparsegpt.hip)."""
+        _gpu(W, "W"), _gpu(Hinv, "Hinv"), _gpu(err, "err")
+        if W.dtype != torch.float32 or Hinv.dtype != torch.float32 or err.dtype != torch.float32:
+            raise EcoflapHipError("SparseGPT works on fp32 copies, as the reference does")
+        if err.numel() != W.shape[0] * int(count):
+            raise EcoflapHipError("err must be [rows, count]")
+        _check(self.lib.ecoflap_sparsegpt_trailing(
+            _ptr(W), W.shape[0], W.shape[1], W.stride(0), _ptr(err), _ptr(Hinv), Hinv.stride(0), int(i1),
+            int(count), int(j0), _stream()), "ecoflap_sparsegpt_trailing")
+
+    def sparsegpt_matrix(self, w, Hinv, dead, blocksize, ranks, prune_n=0, prune_m=0):
+        """The whole of `fasterprune` after the factorisation for one Linear's weight `w` (storage
+        dtype, pruned in place) in ONE host call: widen, every block step with its trailing update,
+        round back.  dead: bool / uint8 [cols] or None; ranks: one python int per column block."""
+        _gpu(w, "w"), _gpu(Hinv, "Hinv")
+        if w.dim() != 2 or w.dtype not in DTYPE_CODE or Hinv.dtype != torch.float32:
+            raise EcoflapHipError("sparsegpt_matrix: a 2-D fp16 / bf16 / fp32 weight and an fp32 Hinv")
+        rows, cols = w.shape
+        if dead is not None:
+            if isinstance(dead, torch.Tensor) and dead.dtype == torch.bool:
+                dead = dead.view(torch.uint8)
+            _gpu(dead, "dead")
+            if dead.dtype != torch.uint8 or dead.numel() != cols:
+                raise EcoflapHipError("dead must be bool / uint8 [cols]")
+        n_blocks = -(-cols // int(blocksize)) if blocksize > 0 else 0
+        ranks_a = None
+        if ranks is not None:
+            if len(ranks) != n_blocks:
+                raise EcoflapHipError("sparsegpt_matrix: one rank per column block")
+            ranks_a = (ctypes.c_int64 * n_blocks)(*[int(k) for k in ranks])
+        nb = self.lib.ecoflap_sparsegpt_matrix_workspace_bytes(rows, cols)
+        ws = self.sgpt_ws.get(nb, w.device)
+        _check(self.lib.ecoflap_sparsegpt_matrix(
+            _ptr(w), DTYPE_CODE[w.dtype], rows, cols, _ptr(Hinv), Hinv.stride(0), _ptr(dead),
+            int(blocksize), ranks_a, int(prune_n), int(prune_m), _ptr(ws), ws.numel(), _stream()),
+            "ecoflap_sparsegpt_matrix")
 
     # ---- K8 ---------------------------------------------------------------------------
     def cholesky(self, H, upper=False):

@@ -15,3 +15,4 @@ from .global_pruner import (  # noqa: F401,E402
     BLIPT5GlobalGradMagAbsPruner, BLIPT5GlobalMagPruner, BLIPT5GlobalMeZoPruner, BLIPT5GlobalPruner,
 )
 from .clip import CLIPLayerWandaPruner  # noqa: F401,E402
+from .clip_sparsegpt import CLIPLayerSparseGPTPruner  # noqa: F401,E402

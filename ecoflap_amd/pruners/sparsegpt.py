@@ -11,7 +11,10 @@ library GEMMs, torch.addmm -> hipBLASLt); the two damped Cholesky factorisations
 inverse from the factor are the build's own fp32 kernels (csrc/cholesky.hip; torch.linalg's
 with `SparseGPT.use_own_cholesky = False`); the per-block threshold + sequential sweep, which
 torch runs as ~1000 small kernels per 128 columns, is one fused HIP step
-(`ecoflap_sparsegpt_block`, csrc/sparsegpt.hip).
+(`ecoflap_sparsegpt_block`, csrc/sparsegpt.hip).  With `SparseGPT.whole_matrix_sweep` (off by
+default; `clip_sparsegpt_pruner` turns it on) the whole sweep of a Linear — the fp32 copy, every
+block step, every trailing update on an fp32 MFMA kernel of the build, the cast back — is ONE host
+call (`ecoflap_sparsegpt_matrix`).
 """
 import math
 
@@ -49,8 +52,11 @@ class SparseGPT:
         """H <- H * n/(n+b) + (sqrt(2/(n+b)) x)^T (sqrt(2/(n+b)) x)   (:71-82)"""
         if len(inp.shape) == 2:
             inp = inp.unsqueeze(0)
-        tmp = inp.shape[0]
-        x = inp.reshape((-1, inp.shape[-1]))
+        self.add_rows(inp.reshape((-1, inp.shape[-1])), inp.shape[0])
+
+    def add_rows(self, x, tmp):
+        """`add_batch` for rows already flattened to [tokens, columns], in any order (a Hessian is a
+        sum over rows), counted as `tmp` samples."""
         if (self.use_mfma_hessian and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
                 and hasattr(self.kernels, "hessian_accum")):
             # fp16 / bf16 activations (the forward under autocast): beta*H + alpha*x^T x on the
@@ -66,7 +72,17 @@ class SparseGPT:
         self.H *= self.nsamples / (self.nsamples + tmp)
         self.nsamples += tmp
         xs = math.sqrt(2 / self.nsamples) * x.float()
-        self.H.addmm_(xs.t(), xs)
+        if self.literal_update:
+            self.H += xs.t().matmul(xs)
+        else:
+            self.H.addmm_(xs.t(), xs)
+
+    # The fp32 update as the reference writes it, `H += inp.matmul(inp.t())`: the product rounded on
+    # its own, then added.  `addmm_` hands H to the GEMM as its accumulator, and a library that
+    # blocks over k then rounds in another order (a CPU GEMM does above a few hundred tokens).
+    # The pruners that came first keep `addmm_` and their recorded hashes; `clip_sparsegpt_pruner`
+    # sets this on its own objects.
+    literal_update = False
 
     def flush(self):
         """Reduce the buffered samples into H (called when the buffer is full and before H is
@@ -213,6 +229,27 @@ class SparseGPT:
         self.factor = (dead, self._damped_cholesky(H, damp, upper=True).contiguous())
         self.H = None
 
+    # The column sweep of a Linear from ONE host call (`ecoflap_sparsegpt_matrix`: the fp32 copy,
+    # every block step, every trailing update on this build's own MFMA kernel, the cast back) where
+    # the backend has the entry and the weight is on the GPU.  Off by default: the trailing update
+    # is then the library GEMM, whose roundings the pruners' recorded hashes hold;
+    # `clip_sparsegpt_pruner` turns it on for its own objects.
+    whole_matrix_sweep = False
+
+    def _one_call_sweep_applies(self, blocksize):
+        w = self.layer.weight.data
+        return (self.whole_matrix_sweep and w.is_cuda and w.dim() == 2 and w.is_contiguous()
+                and 0 < blocksize <= 128 and hasattr(self.kernels, "sparsegpt_matrix"))
+
+    def _sweep_in_one_call(self, sparsity, prune_n, prune_m, blocksize):
+        dead, Hinv = self.factor
+        ranks = None
+        if prune_n == 0:                                   # int(tmp.numel() * sparsity) (:187)
+            ranks = [int(self.rows * (min(i1 + blocksize, self.columns) - i1) * sparsity)
+                     for i1 in range(0, self.columns, blocksize)]
+        with PhaseTimer.span("sparsegpt.sweep (one call: csrc/sparsegpt.hip)"):
+            self.kernels.sparsegpt_matrix(self.layer.weight.data, Hinv, dead, blocksize, ranks, prune_n, prune_m)
+
     def fasterprune(self, sparsity, prune_n=0, prune_m=0, blocksize=128, percdamp=.01,
                     same_hessian_as=None):
         """`same_hessian_as`: a SparseGPT of this block that saw the very same inputs (q/k/v,
@@ -220,6 +257,15 @@ class SparseGPT:
         been pruned — its dead-column mask and factor Hinv depend on H only and are reused
         instead of being recomputed (two Cholesky factorisations and an inverse each)."""
         self.flush()
+        if self._one_call_sweep_applies(blocksize):
+            src = self if same_hessian_as is None or same_hessian_as.factor is None else same_hessian_as
+            if src.factor is None:
+                with PhaseTimer.span("sparsegpt.factor (clamp, 2 damped Cholesky, inverse: csrc/cholesky.hip)"):
+                    self._factor_alone(percdamp)
+            self.H = None
+            self.factor = src.factor
+            self._sweep_in_one_call(sparsity, prune_n, prune_m, blocksize)
+            return
         W = self.layer.weight.data.clone().float()
         H = self.H
         self.H = None

@@ -13,13 +13,16 @@ output read in place, causal in the text tower), and the patch embedding is one 
 (`fused.patches_gemm`, no MIOpen: DESIGN §5).  Where the kernel refuses a shape (head width other
 than 64, more than 224 tokens) the block stays on `nn.MultiheadAttention`.
 
-`clip_wanda_pruner` (pruners/clip.py) prunes these towers.  While its stage 2 hooks a block, the
+`clip_wanda_pruner` (pruners/clip.py) and `clip_sparsegpt_pruner` (pruners/clip_sparsegpt.py) prune
+these towers.  While stage 2 hooks a block, the
 block reports the operands of the two attention projections, which no `nn.Linear` hook can see
 (`_stat_sink`, off by default: `attention()` then is the code above, unchanged): `ln_1(x)` for the
 in-projection, and for the out-projection the output of the reference's UNMASKED side copy of the
 attention (CoOp/trainers/pruners/wanda_pruner.py:300-322) — on the GPU in fp16 as the column
 statistic `fused.mha_attention_colsq` leaves (in the visual tower the same kernel call that
-produces the block's output), everywhere else as the reference's literal op chain in torch.
+produces the block's output), everywhere else as the reference's literal op chain in torch.  A sink
+that answers `takes_kernel_operand()` (SparseGPT: a Hessian needs the rows themselves) gets the
+unmasked `fused.mha_attention` output instead of the statistic, as a view of `[L, N, D]`.
 
 Not here yet: `stage_plan()`."""
 import math
@@ -83,7 +86,8 @@ class ResidualAttentionBlock(nn.Module):
         y = fused.mha_attention(qkv, a.num_heads, a.head_dim ** -0.5, causal=causal, seq_first=True)
         return None if y is None else a.out_proj(y)
 
-    # stage 2 of `clip_wanda_pruner` sets this on the block it hooks (pruners/clip.py::_AttentionSites)
+    # stage 2 of the CLIP pruners sets this on the block it hooks (pruners/clip.py::_AttentionSites,
+    # pruners/clip_sparsegpt.py::_HessianSites)
     _stat_sink = None
 
     def _side_attention(self, x):
@@ -109,7 +113,20 @@ class ResidualAttentionBlock(nn.Module):
                         or x.dim() != 3 or a.in_proj_weight is None
                         or a.in_proj_weight.dtype != torch.float16)
         causal = self._mask_is_causal(x.shape[0]) if fused_ok else None
-        if causal is not None and sink.takes_statistic():
+        if causal is not None and getattr(sink, "takes_kernel_operand", bool)():
+            # the out-projection's OPERAND from the kernels (a Hessian needs the rows, not their
+            # column norms): in the visual tower it is the block's own attention output; in the text
+            # tower one more, unmasked, call beside the causal forward.  [L, N, D] as it lies.
+            from . import fused
+            qkv = F.linear(x, a.in_proj_weight, a.in_proj_bias)         # [L, N, 3D]
+            scale = a.head_dim ** -0.5
+            y = fused.mha_attention(qkv, a.num_heads, scale, causal=causal, seq_first=True)
+            side = y if (y is None or not causal) else fused.mha_attention(
+                qkv, a.num_heads, scale, causal=False, seq_first=True)
+            if side is not None:
+                sink.operand("attn.out_proj", side.permute(1, 0, 2))
+                return a.out_proj(y)
+        elif causal is not None and sink.takes_statistic():
             from . import fused
             qkv = F.linear(x, a.in_proj_weight, a.in_proj_bias)         # [L, N, 3D]
             scale = a.head_dim ** -0.5

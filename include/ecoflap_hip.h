@@ -404,6 +404,38 @@ int ecoflap_sparsegpt_block_nm(float* W, int64_t rows, int64_t ldw, const float*
                                int64_t i1, int count, int n, int m, float* err_out,
                                uint8_t* mask_out, void* stream);
 
+/* The trailing update of a block step,
+ * replaces  W[:, i2:] -= Err1.matmul(Hinv[i1:i2, i2:])
+ *     CoOp/trainers/pruners/sparsegpt_pruner.py:302 (LAVIS/.../sparsegpt_pruner.py:216)
+ * as  W[:, j0:cols] -= Err[rows, count] @ Hinv[i1:i1+count, j0:cols]  on the fp32 working copy
+ * W[rows, ldw] (v_mfma_f32_32x32x2_f32).  Err: float[rows, count] as ecoflap_sparsegpt_block leaves
+ * it (pitch `count`, count <= 128); Hinv: float[*, ldh].  Any rows, any tail width; ldw, ldh >= cols.
+ * Every element is one fp32 accumulation chain over k in a fixed order, then one subtraction: no
+ * atomics, no split over k, the same call gives the same bits.  j0 == cols: nothing to do.
+ * No workspace, asynchronous. */
+int ecoflap_sparsegpt_trailing(float* W, int64_t rows, int64_t cols, int64_t ldw, const float* Err,
+                               const float* Hinv, int64_t ldh, int64_t i1, int count, int64_t j0,
+                               void* stream);
+
+/* The whole column sweep of one Linear from one host call,
+ * replaces SparseGPT.fasterprune after the factorisation
+ *     CoOp/trainers/pruners/sparsegpt_pruner.py:176-189 (W = w.float(); W[:, dead] = 0),
+ *     :261-302 (per `blocksize` columns: threshold, sweep, trailing update), :307 (w = W.to(dtype)).
+ * w: [rows, cols] contiguous in `dtype` (fp16 / bf16 / fp32), read and written in place.
+ * Hinv: float[cols, ldh], upper factor.  dead (optional): DEVICE uint8[cols], nonzero = the
+ * column's Hessian diagonal was 0.  blocksize <= 128.  ranks_host: HOST int64[ceil(cols /
+ * blocksize)], per column block k = int(rows * count * sparsity) in the reference's double
+ * arithmetic (read before the call returns; may be NULL under n:m).  prune_n / prune_m: 0, 0 or the
+ * n:m step of ecoflap_sparsegpt_block_nm.  workspace: >= ecoflap_sparsegpt_matrix_workspace_bytes
+ * (the fp32 working copy, Err[rows, 128], the selection state), 16-byte aligned, caller-owned.
+ * Arguments are checked before anything is queued; then launches only, no host synchronisation.
+ * Bit for bit the same steps issued one by one through the entries above. */
+size_t ecoflap_sparsegpt_matrix_workspace_bytes(int64_t rows, int64_t cols);
+int ecoflap_sparsegpt_matrix(void* w, int dtype, int64_t rows, int64_t cols, const float* Hinv,
+                             int64_t ldh, const uint8_t* dead, int blocksize,
+                             const int64_t* ranks_host, int prune_n, int prune_m, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* SparseGPT Hessian accumulation, the path's one GEMM-shaped
  * contraction, on the matrix cores:
  * replaces SparseGPT.add_batch   LAVIS/lavis/compression/pruners/sparsegpt_pruner.py:71-82
