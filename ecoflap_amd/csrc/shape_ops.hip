@@ -162,6 +162,27 @@ __global__ __launch_bounds__(256) void gelu_mul_kernel(const void* __restrict__ 
     }
 }
 
+// LLaMA MLP (SwiGLU): y = silu(a) * b, silu = a / (1 + exp(-a)) in fp32 (the fast exponential),
+// rounded to dtype, then the product rounded to dtype — torch's two ops in one pass
+template <int DT>
+__global__ __launch_bounds__(256) void silu_mul_kernel(const void* __restrict__ a,
+                                                       const void* __restrict__ b,
+                                                       void* __restrict__ y, int64_t nvec) {
+    constexpr int N = Vec<DT>::N;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < nvec; v += stride) {
+        float fa[N], fb[N];
+        Vec<DT>::unpack(ld16(a, v), fa);
+        Vec<DT>::unpack(ld16(b, v), fb);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const float g = fa[i] / (1.0f + __expf(-fa[i]));
+            fa[i] = Vec<DT>::round(g) * fb[i];
+        }
+        st16(y, v, Vec<DT>::pack(fa));
+    }
+}
+
 static int t5_rmsnorm_impl(const void* x, const void* residual, const void* w, void* sum_out, void* y,
                            int64_t rows, int64_t d, float eps, int dtype, void* stream) {
     if (dtype != ECOFLAP_F16 && dtype != ECOFLAP_BF16) return ECOFLAP_EDTYPE;
@@ -204,6 +225,24 @@ extern "C" int ecoflap_gelu_mul(const void* a, const void* b, void* y, int64_t n
         hipLaunchKernelGGL((gelu_mul_kernel<ECOFLAP_F16>), dim3((unsigned)blocks), dim3(256), 0, s, a, b, y, nvec);
     else
         hipLaunchKernelGGL((gelu_mul_kernel<ECOFLAP_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, a, b, y, nvec);
+    ECO_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ecoflap_silu_mul(const void* a, const void* b, void* y, int64_t n, int dtype,
+                                void* stream) {
+    if (dtype != ECOFLAP_F16 && dtype != ECOFLAP_BF16) return ECOFLAP_EDTYPE;
+    if (n <= 0 || n % 8 != 0) return ECOFLAP_ESIZE;
+    if (!a || !b || !y) return ECOFLAP_ENULL;
+    if (!aligned16(a) || !aligned16(b) || !aligned16(y)) return ECOFLAP_EALIGN;
+    const int64_t nvec = n / 8;
+    int64_t blocks = (nvec + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == ECOFLAP_F16)
+        hipLaunchKernelGGL((silu_mul_kernel<ECOFLAP_F16>), dim3((unsigned)blocks), dim3(256), 0, s, a, b, y, nvec);
+    else
+        hipLaunchKernelGGL((silu_mul_kernel<ECOFLAP_BF16>), dim3((unsigned)blocks), dim3(256), 0, s, a, b, y, nvec);
     ECO_CHECK_LAUNCH();
     return 0;
 }

@@ -29,6 +29,7 @@ def _get():
         lib.ecoflap_t5_rmsnorm.argtypes = [vp, vp, vp, i64, i64, f32, ci, vp]
         lib.ecoflap_t5_add_rmsnorm.argtypes = [vp, vp, vp, vp, vp, i64, i64, f32, ci, vp]
         lib.ecoflap_gelu_mul.argtypes = [vp, vp, vp, i64, ci, vp]
+        lib.ecoflap_silu_mul.argtypes = [vp, vp, vp, i64, ci, vp]
         lib.ecoflap_add_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, f32, ci, vp]
         lib.ecoflap_add_bias_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, f32, ci, vp]
         lib.ecoflap_bias_gelu.argtypes = [vp, vp, vp, i64, i64, ci, vp]
@@ -42,6 +43,8 @@ def _get():
         lib.ecoflap_mha_attention_colsq_workspace_bytes.argtypes = [i64, i64]
         lib.ecoflap_mha_attention_colsq.argtypes = [vp, vp, vp, vp, ctypes.c_size_t, i64, i64, i64, i64,
                                                     i64, i64, i64, i64, f32, ci, vp]
+        lib.ecoflap_causal_attention.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
+                                                 f32, ci, vp]
         lib.ecoflap_multi_copy.argtypes = [vp, ci, vp]
         lib.ecoflap_multi_compare.argtypes = [vp, ci, vp, vp]
         _lib = lib
@@ -104,6 +107,22 @@ def gelu_mul(a, b):
                                  _hip.DTYPE_CODE[ac.dtype], _stream())
     if rc != 0:
         raise _hip.EcoflapHipError(f"ecoflap_gelu_mul failed ({rc})")
+    return y
+
+
+def silu_mul(a, b):
+    """silu(a) * b of the LLaMA MLP (`act_fn(gate_proj(x)) * up_proj(x)`) in one pass, torch's
+    bits up to the exponential: silu in fp32 rounded to the dtype, then the product rounded
+    (`ecoflap_silu_mul`).  -> tensor or None (caller runs the two torch ops)."""
+    if not _usable(a, b) or a.numel() % 8 != 0 or a.numel() == 0 or a.shape != b.shape:
+        return None
+    ac = a if a.is_contiguous() else a.contiguous()
+    bc = b if b.is_contiguous() else b.contiguous()
+    y = torch.empty_like(ac)
+    rc = _get().ecoflap_silu_mul(ac.data_ptr(), bc.data_ptr(), y.data_ptr(), ac.numel(),
+                                 _hip.DTYPE_CODE[ac.dtype], _stream())
+    if rc != 0:
+        raise _hip.EcoflapHipError(f"ecoflap_silu_mul failed ({rc})")
     return y
 
 
@@ -226,6 +245,46 @@ def mha_attention(qkv, heads, scale, causal=False, seq_first=True):
         return None
     if rc != 0:
         raise _hip.EcoflapHipError(f"ecoflap_mha_attention failed ({rc})")
+    return out
+
+
+def causal_attention(q, k, v, heads, scale, rope=None):
+    """softmax(rot(q) rot(k)^T * scale + causal mask) v per (sample, head) of a LLaMA decoder block,
+    straight from the outputs of the q / k / v projections — three [B, T, heads * 128] fp16 tensors
+    with the same strides (three tensors, or three slices of one buffer: read in place) — into the
+    merged heads [B, T, heads * 128], contiguous (`ecoflap_causal_attention`,
+    csrc/causal_attention.hip).  rope: None (no rotation) or (cos, sin), fp32 [T, 64] on the
+    device: the rotate_half rotary embedding of positions 0 .. T - 1, applied inside the kernel.
+    -> tensor or None (caller runs the torch op chain): the refusal rules of `mha_attention`, and
+    the shapes the kernel does not serve (head width != 128, more than 4096 tokens)."""
+    import os
+    if (torch.is_grad_enabled() or q.device.type != "cuda" or q.dtype != torch.float16 or q.dim() != 3
+            or os.environ.get("ECOFLAP_NO_FUSED_ATTENTION")):
+        return None
+    for t in (q, k, v):
+        if (t.dtype != q.dtype or t.device != q.device or t.shape != q.shape or t.stride() != q.stride()
+                or t.stride(2) != 1):
+            return None
+    B, T, C = q.shape
+    if heads < 1 or C != heads * 128 or not (1 <= T <= 4096) or B < 1 or not (0.0 < float(scale) < float("inf")):
+        return None
+    cos = sin = None
+    if rope is not None:
+        cos, sin = rope
+        for t in (cos, sin):
+            if (t.dtype != torch.float32 or t.device != q.device or tuple(t.shape) != (T, 64)
+                    or not t.is_contiguous()):
+                return None
+    out = torch.empty(B, T, C, dtype=q.dtype, device=q.device)
+    rc = _get().ecoflap_causal_attention(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+        None if cos is None else cos.data_ptr(), None if sin is None else sin.data_ptr(),
+        B, T, heads, 128, q.stride(1), q.stride(0), out.stride(1), out.stride(0), float(scale),
+        _hip.DTYPE_CODE[q.dtype], _stream())
+    if rc in (-3, -5):      # ECOFLAP_ESIZE / ECOFLAP_EALIGN: a view the kernel cannot address in place
+        return None
+    if rc != 0:
+        raise _hip.EcoflapHipError(f"ecoflap_causal_attention failed ({rc})")
     return out
 
 

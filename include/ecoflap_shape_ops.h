@@ -29,6 +29,10 @@ int ecoflap_t5_add_rmsnorm(const void* x, const void* residual, const void* w, v
  * (erf GELU in fp32, rounded to dtype, then the product rounded to dtype). n % 8 == 0. */
 int ecoflap_gelu_mul(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream);
 
+/* SwiGLU of the LLaMA MLP (transformers' LlamaMLP: act_fn(gate_proj(x)) * up_proj(x)):
+ * y = dtype(dtype(silu(a)) * b), silu(a) = a / (1 + exp(-a)) in fp32.  F16 / BF16; n % 8 == 0. */
+int ecoflap_silu_mul(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream);
+
 /* nn.LayerNorm on a 16-bit activation under autocast (EVA ViT blocks,
  * LAVIS/lavis/models/eva_vit.py:160-184): fp32 statistics and fp32 affine parameters, 16-bit
  * in and out; with `residual` the block's residual add is fused in front:
@@ -114,6 +118,34 @@ int ecoflap_mha_attention_colsq(const void* qkv, void* out, float* sq, void* wor
                                 int64_t head_dim, int64_t qkv_token_stride, int64_t qkv_batch_stride,
                                 int64_t out_token_stride, int64_t out_batch_stride, float scale,
                                 int dtype, void* stream);
+
+/* Causal self-attention of a LLaMA decoder block (transformers' LlamaAttention, eager path, between
+ * the q / k / v projections and o_proj), rotary embedding included (csrc/causal_attention.hip):
+ *   out = softmax(rot(q) rot(k)^T * scale + causal mask) v   per (sample, head)
+ * Key j > query i has probability exactly 0.  The row of (sample b, token n) of q, k and v starts at
+ * ptr + b * qkv_batch_stride + n * qkv_token_stride (elements) and holds [heads, 128]: the three
+ * Linears' outputs are read in place, as three tensors or as three slices of one; out's row of
+ * (b, n) starts at out + b * out_batch_stride + n * out_token_stride and receives the merged heads
+ * [heads, 128].  rot is the rotate_half form (element d pairs with d + 64, NOT the interleaved form):
+ *   rot(x)[d] = x[d] cos[n, d] - x[d + 64] sin[n, d],  rot(x)[d + 64] = x[d + 64] cos[n, d] + x[d] sin[n, d]
+ * with token n's row of rope_cos / rope_sin, [tokens, 64] fp32 on the device (positions 0 ..
+ * tokens - 1, no KV cache; rope_theta and scaling variants are the caller's); multiplied in fp32,
+ * rotated q and k rounded once to f16, no rotated copy in memory.  Both table pointers NULL: no
+ * rotation; one alone: ECOFLAP_ENULL.  Grouped-query attention (kv_heads != heads) is not served.
+ * F16 only (else ECOFLAP_EDTYPE); head_dim == 128, 1 <= tokens <= 4096, batch, heads > 0, batch *
+ * heads * ceil(tokens / 32) < 2^31, finite scale > 0, token strides at least a row, batch strides
+ * >= 0 (else ECOFLAP_ESIZE); pointers 16-byte aligned and every stride a multiple of 8 elements
+ * (else ECOFLAP_EALIGN).  Flash-style: key / value blocks of 64 stream through LDS, running
+ * maximum and sum per query with a rescale on every block (no deferred-rescale threshold), fp32
+ * scores and sums, probabilities rounded to f16 for the second product; key blocks above the
+ * diagonal are skipped.  No atomics; every (sample, head, 256-query block) is computed
+ * independently (batch invariant bit for bit).  Nothing is launched on an error. */
+int ecoflap_causal_attention(const void* q, const void* k, const void* v, void* out,
+                             const float* rope_cos, const float* rope_sin, int64_t batch,
+                             int64_t tokens, int64_t heads, int64_t head_dim,
+                             int64_t qkv_token_stride, int64_t qkv_batch_stride,
+                             int64_t out_token_stride, int64_t out_batch_stride, float scale,
+                             int dtype, void* stream);
 
 /* Up to ECOFLAP_COPY_MAX_ITEMS device-to-device copies (non-overlapping, any alignment) in
  * one launch: the loop's state hand-overs between static graph buffers. */
