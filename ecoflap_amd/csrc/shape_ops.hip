@@ -163,7 +163,10 @@ __global__ __launch_bounds__(256) void gelu_mul_kernel(const void* __restrict__ 
 }
 
 // LLaMA MLP (SwiGLU): y = silu(a) * b, silu = a / (1 + exp(-a)) in fp32 (the fast exponential),
-// rounded to dtype, then the product rounded to dtype — torch's two ops in one pass
+// rounded to dtype, then the product rounded to dtype — torch's two ops in one pass.
+// a < -88.7: exp(-a) is inf in fp32 and a / inf = -0, while silu(a) = a * exp(a) is a normal bf16
+// value down to a = -92 (2e-37 at -89): there the exponential is taken in two halves, which keeps
+// every factor normal.  Every other argument keeps the quotient's bits.
 template <int DT>
 __global__ __launch_bounds__(256) void silu_mul_kernel(const void* __restrict__ a,
                                                        const void* __restrict__ b,
@@ -176,7 +179,12 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const void* __restrict__ 
         Vec<DT>::unpack(ld16(b, v), fb);
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            const float g = fa[i] / (1.0f + __expf(-fa[i]));
+            const float e = __expf(-fa[i]);
+            float g = fa[i] / (1.0f + e);
+            if (e == INFINITY) {
+                const float h = __expf(0.5f * fa[i]);
+                g = (fa[i] * h) * h;
+            }
             fa[i] = Vec<DT>::round(g) * fb[i];
         }
         st16(y, v, Vec<DT>::pack(fa));
@@ -254,6 +262,9 @@ static int add_layernorm_impl(const void* x, const void* residual, const void* r
     if (rows < 0 || d <= 0 || (d % 8) != 0) return ECOFLAP_ESIZE;
     if (rows == 0) return 0;
     if (!x || !w || !b || !y || (residual && !sum_out) || (residual_bias && !residual)) return ECOFLAP_ENULL;
+    if (!aligned16(x) || !aligned16(w) || !aligned16(b) || !aligned16(y) ||
+        (residual && (!aligned16(residual) || !aligned16(sum_out))) || (residual_bias && !aligned16(residual_bias)))
+        return ECOFLAP_EALIGN;
     const dim3 grid((unsigned)((rows + 3) / 4)), blk(256);
     hipStream_t s = (hipStream_t)stream;
     if (dtype == ECOFLAP_F16)
@@ -347,6 +358,7 @@ extern "C" int ecoflap_qkv_bias_add(void* qkv, const float* q_bias, const float*
     if (rows < 0 || dim <= 0 || (dim % 8) != 0) return ECOFLAP_ESIZE;
     if (rows == 0) return 0;
     if (!qkv || !q_bias || !v_bias) return ECOFLAP_ENULL;
+    if (!aligned16(qkv) || !aligned16(q_bias) || !aligned16(v_bias)) return ECOFLAP_EALIGN;
     int64_t b = (rows * 3 * dim / 8 + 255) / 256;
     if (b > 4096) b = 4096;
     const dim3 grid((unsigned)b), blk(256);

@@ -134,11 +134,13 @@ def add_layernorm(x, residual, norm, residual_bias=None):
     if (torch.is_grad_enabled() or x.device.type != "cuda"
             or x.dtype not in (torch.float16, torch.bfloat16) or x.shape[-1] % 8 != 0
             or norm.weight is None or norm.bias is None or norm.weight.dtype != torch.float32
-            or not torch.is_autocast_enabled()):
+            or norm.bias.dtype != torch.float32 or norm.weight.device != x.device
+            or norm.bias.device != x.device or not torch.is_autocast_enabled()):
         return None
     if residual is not None and (residual.dtype != x.dtype or residual.shape != x.shape):
         return None
     if residual_bias is not None and (residual is None or residual_bias.dtype != x.dtype
+                                      or residual_bias.device != x.device
                                       or residual_bias.numel() != x.shape[-1]
                                       or not residual_bias.is_contiguous()):
         return None
@@ -152,6 +154,8 @@ def add_layernorm(x, residual, norm, residual_bias=None):
             xc.data_ptr(), rc_.data_ptr(), residual_bias.data_ptr(), norm.weight.data_ptr(),
             norm.bias.data_ptr(), s.data_ptr(), y.data_ptr(),
             xc.numel() // d, d, float(norm.eps), _hip.DTYPE_CODE[xc.dtype], _stream())
+        if rc == -5:        # ECOFLAP_EALIGN: a view that does not start on 16 bytes
+            return None
         if rc != 0:
             raise _hip.EcoflapHipError(f"ecoflap_add_bias_layernorm failed ({rc})")
         return s, y
@@ -159,6 +163,8 @@ def add_layernorm(x, residual, norm, residual_bias=None):
         xc.data_ptr(), None if rc_ is None else rc_.data_ptr(), norm.weight.data_ptr(),
         norm.bias.data_ptr(), None if rc_ is None else s.data_ptr(), y.data_ptr(),
         xc.numel() // d, d, float(norm.eps), _hip.DTYPE_CODE[xc.dtype], _stream())
+    if rc == -5:
+        return None
     if rc != 0:
         raise _hip.EcoflapHipError(f"ecoflap_add_layernorm failed ({rc})")
     return s, y
@@ -176,6 +182,8 @@ def qkv_bias_add(qkv, q_bias, v_bias):
     rc = _get().ecoflap_qkv_bias_add(qkv.data_ptr(), q_bias.data_ptr(), v_bias.data_ptr(),
                                      qkv.numel() // (3 * dim), dim, _hip.DTYPE_CODE[qkv.dtype],
                                      _stream())
+    if rc == -5:            # ECOFLAP_EALIGN (nothing was written)
+        return None
     if rc != 0:
         raise _hip.EcoflapHipError(f"ecoflap_qkv_bias_add failed ({rc})")
     return qkv
@@ -622,7 +630,8 @@ def _pinned_forward(self, x):
     # a forward hook, a feature reader — gets the full Linear.  Why at all: the pinned solutions have no bias epilogue on gfx950,
     # and a bias prefill + beta = 1 costs a write and a read of the output (measured: -10 % on
     # the bench).  The flag the consumer reads says whether THIS call left the bias out.
-    if self.bias is not None and self.__dict__.get("_defer_now"):
+    # (only a bias of the weight's dtype: the consumers read it as a row of the output's dtype)
+    if self.bias is not None and self.bias.dtype == self.weight.dtype and self.__dict__.get("_defer_now"):
         y = linear(x, self.weight, None, library_bias=self.bias)
         if y is not None:
             self._bias_pending = True
@@ -661,10 +670,18 @@ def take_pending_bias(mod):
     return None
 
 
+def _bias_row_ok(bias, like):
+    """`bias` is what the bias consumers' kernels read: [d] of `like`'s dtype on its device, whole
+    16-byte vectors."""
+    return (bias.dtype == like.dtype and bias.device == like.device and bias.is_contiguous()
+            and bias.numel() == like.shape[-1] and bias.data_ptr() % 16 == 0)
+
+
 def bias_gelu(a, bias):
     """gelu(a + bias) for a Linear output without its bias (erf GELU): one fused kernel for
     16-bit GPU tensors, the torch op chain otherwise (an fp32 Linear on the build's own GEMM)."""
-    if a.dtype not in (torch.float16, torch.bfloat16) or a.device.type != "cuda" or a.shape[-1] % 8:
+    if (a.dtype not in (torch.float16, torch.bfloat16) or a.device.type != "cuda" or a.shape[-1] % 8
+            or a.numel() == 0 or not _bias_row_ok(bias, a)):
         return torch.nn.functional.gelu(a + bias)
     ac = a if a.is_contiguous() else a.contiguous()
     y = torch.empty_like(ac)
@@ -680,7 +697,7 @@ def bias_add_residual(x, m, bias):
     """x + (m + bias) for a Linear output m without its bias: one fused kernel for 16-bit GPU
     tensors, the torch ops otherwise."""
     if (x.dtype not in (torch.float16, torch.bfloat16) or x.device.type != "cuda" or x.shape[-1] % 8
-            or m.dtype != x.dtype or m.shape != x.shape):
+            or m.dtype != x.dtype or m.shape != x.shape or x.numel() == 0 or not _bias_row_ok(bias, x)):
         return x + (m + bias)
     xc = x if x.is_contiguous() else x.contiguous()
     mc = m if m.is_contiguous() else m.contiguous()

@@ -30,7 +30,8 @@ int ecoflap_t5_add_rmsnorm(const void* x, const void* residual, const void* w, v
 int ecoflap_gelu_mul(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream);
 
 /* SwiGLU of the LLaMA MLP (transformers' LlamaMLP: act_fn(gate_proj(x)) * up_proj(x)):
- * y = dtype(dtype(silu(a)) * b), silu(a) = a / (1 + exp(-a)) in fp32.  F16 / BF16; n % 8 == 0. */
+ * y = dtype(dtype(silu(a)) * b), silu(a) = a / (1 + exp(-a)) in fp32 (a * exp(a / 2) * exp(a / 2)
+ * where exp(-a) overflows, a < -88.7).  F16 / BF16; n % 8 == 0. */
 int ecoflap_silu_mul(const void* a, const void* b, void* y, int64_t n, int dtype, void* stream);
 
 /* nn.LayerNorm on a 16-bit activation under autocast (EVA ViT blocks,
@@ -38,7 +39,9 @@ int ecoflap_silu_mul(const void* a, const void* b, void* y, int64_t n, int dtype
  * in and out; with `residual` the block's residual add is fused in front:
  *   s = dtype(x + residual) -> sum_out;  y = dtype((float(s) - mean) * rstd * w + b)
  * x, residual, sum_out, y: [rows, d] of `dtype` (F16/BF16); w, b: [d] float; d % 8 == 0.
- * residual == NULL: plain LayerNorm of x (sum_out unused). */
+ * residual == NULL: plain LayerNorm of x (sum_out unused).  Every pointer, w and b included, is
+ * read or written in 16-byte vectors: ECOFLAP_EALIGN otherwise (ecoflap_add_bias_layernorm and
+ * ecoflap_qkv_bias_add below too). */
 int ecoflap_add_layernorm(const void* x, const void* residual, const float* w, const float* b,
                           void* sum_out, void* y, int64_t rows, int64_t d, float eps, int dtype,
                           void* stream);

@@ -2,6 +2,14 @@ import numpy as np
 import torch
 
 NP2T = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+FORMAT = {torch.float16: (10, -14), torch.bfloat16: (7, -126)}      # mantissa bits, smallest normal exponent
+
+
+def _ulp(y64, dtype):
+    """The spacing of `dtype` at |y64| (fp64 tensor); under the smallest normal: one subnormal step."""
+    bits, emin = FORMAT[dtype]
+    e = torch.floor(torch.log2(y64.abs().clamp_min(2.0 ** emin)))
+    return torch.exp2(e - bits)
 
 
 def from_bits(a, dtype):

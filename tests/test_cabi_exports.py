@@ -156,6 +156,30 @@ def test_argument_errors_of_the_later_entry_points():
     assert lib.ecoflap_add_layernorm(vp(16), None, vp(16), vp(16), None, vp(16), 4, 12, 1e-6, 1, None) == -3
     assert lib.ecoflap_add_layernorm(vp(16), None, vp(16), vp(16), None, vp(16), 4, 16, 1e-6, 0, None) == -1
     assert lib.ecoflap_add_layernorm(vp(16), vp(16), vp(16), vp(16), None, vp(16), 4, 16, 1e-6, 1, None) == -2
+    # every pointer is read or written in 16-byte vectors, the fp32 w / b and the 16-bit
+    # residual_bias included: EALIGN, as the sibling entry points answer
+    i64 = ctypes.c_int64
+    ok = [vp(16), vp(16), vp(16), vp(16), vp(16), vp(16)]               # x, residual, w, b, sum_out, y
+    for bad in range(6):
+        p = list(ok)
+        p[bad] = vp(8)
+        assert lib.ecoflap_add_layernorm(*p, 4, 16, 1e-6, 1, None) == -5, bad
+    for bad in (0, 2, 3, 5):                                            # without a residual
+        p = list(ok)
+        p[bad], p[1], p[4] = vp(8), None, None
+        assert lib.ecoflap_add_layernorm(*p, 4, 16, 1e-6, 1, None) == -5, bad
+    lib.ecoflap_add_bias_layernorm.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_float, ctypes.c_int, vp]
+    for bad in range(7):                                                # x, residual, residual_bias, w, b, sum_out, y
+        p = [vp(16)] * 7
+        p[bad] = vp(8)
+        assert lib.ecoflap_add_bias_layernorm(*p, 4, 16, 1e-6, 2, None) == -5, bad
+    lib.ecoflap_qkv_bias_add.argtypes = [vp, vp, vp, i64, i64, ctypes.c_int, vp]
+    for bad in range(3):                                                # qkv, q_bias, v_bias
+        p = [vp(16)] * 3
+        p[bad] = vp(8)
+        assert lib.ecoflap_qkv_bias_add(*p, 4, 16, 1, None) == -5, bad
+    assert lib.ecoflap_qkv_bias_add(vp(16), None, vp(16), 4, 16, 1, None) == -2
+    assert lib.ecoflap_qkv_bias_add(vp(8), vp(8), vp(8), 0, 16, 1, None) == 0     # no rows: nothing is read
 
 
 def test_argument_errors_of_the_round2_entry_points():

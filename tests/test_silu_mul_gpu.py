@@ -10,15 +10,9 @@ fast exponential."""
 import pytest
 import torch
 
+from helpers import _ulp
+
 pytestmark = pytest.mark.gpu
-
-FORMAT = {torch.float16: (10, -14), torch.bfloat16: (7, -126)}      # mantissa bits, smallest normal exponent
-
-
-def _ulp(y64, dtype):
-    bits, emin = FORMAT[dtype]
-    e = torch.floor(torch.log2(y64.abs().clamp_min(2.0 ** emin)))
-    return torch.exp2(e - bits)
 
 
 @pytest.mark.parametrize("n", [8, 4104, 11008 * 3])
