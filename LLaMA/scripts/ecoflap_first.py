@@ -1,0 +1,23 @@
+"""ECoFLaP (first order) + Wanda on LLaMA-7B (reference: LLaMA/scripts/ecoflap_first.sh — the flags
+of ecoflap_zero.sh without `--use_mezo`; `--num_samples_for_first_stage` keeps main.py's default,
+128).  Stage 1 runs under autograd: the fused forward ops refuse there and torch's op chain runs
+(not optimised).
+
+    python LLaMA/scripts/ecoflap_first.py [extra harness flags]
+
+Outputs go under out/llama_7b/unstructured/ecoflap_first0.6/ with --save_pruned_model."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _llama_launch import harness_flags, run  # noqa: E402
+
+NUM_SAMPLES_FOR_FIRST_STAGE = 128
+
+
+def flags():
+    return harness_flags("ecoflap_first", "GradOnly_sum", NUM_SAMPLES_FOR_FIRST_STAGE)
+
+
+if __name__ == "__main__":
+    sys.exit(run(flags(), sys.argv[1:]))

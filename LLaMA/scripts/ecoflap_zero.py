@@ -1,0 +1,25 @@
+"""ECoFLaP (zeroth order) + Wanda on LLaMA-7B (reference: LLaMA/scripts/ecoflap_zero.sh — `main.py
+--model huggyllama/llama-7b --prune_method wanda --sparsity_ratio 0.6 --sparsity_type unstructured
+--approach_for_sparsity block --aggregate_method sum --score_method GradOnly --max_sparsity_per_layer
+0.7 --use_mezo --num_samples_for_first_stage 32`, 128 calibration samples of 2048 tokens, seed 0).
+The model is the random-init decoder of that shape and the calibration ids are synthetic; the
+perplexity evaluation behind the pruning is the model zoo's and is not reproduced.
+
+    python LLaMA/scripts/ecoflap_zero.py [extra harness flags]
+
+Outputs go under out/llama_7b/unstructured/ecoflap_zero0.6/ with --save_pruned_model."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _llama_launch import harness_flags, run  # noqa: E402
+
+NUM_SAMPLES_FOR_FIRST_STAGE = 32
+
+
+def flags():
+    return harness_flags("ecoflap_zero", "MEZO-GradOnly_sum", NUM_SAMPLES_FOR_FIRST_STAGE)
+
+
+if __name__ == "__main__":
+    sys.exit(run(flags(), sys.argv[1:]))

@@ -27,9 +27,10 @@ import yaml
 
 def build_parser():
     p = argparse.ArgumentParser(description="ECoFLaP pruning on MI355X (hot path only)")
-    p.add_argument("--shape", default="blip2", choices=["blip2", "t5", "vit", "clip"],
+    p.add_argument("--shape", default="blip2", choices=["blip2", "t5", "vit", "clip", "llama"],
                    help="blip2: EVA-ViT-g + Q-Former + FlanT5-XL; t5: FlanT5-XL; vit: ViT-B/16 CLIP shape; "
-                        "clip: OpenAI-CLIP ViT-B/16, both towers (CoOp's zero-shot trainer)")
+                        "clip: OpenAI-CLIP ViT-B/16, both towers (CoOp's zero-shot trainer); "
+                        "llama: LLaMA-7B decoder in fp16 at 2048 tokens (LLaMA/main.py)")
     p.add_argument("--toy", action="store_true", help="CPU-sized shapes of the same families")
     p.add_argument("--device", default="cuda")
     # the reference's flags (names, types, defaults)
@@ -44,6 +45,8 @@ def build_parser():
     # CoOp/train.py's two spec flags (--shape clip)
     p.add_argument("--visual_prune_spec", type=str, default=None)
     p.add_argument("--language_prune_spec", type=str, default=None)
+    # --shape llama: "<layers>-<keep>-1-1", keep = 1 - LLaMA/main.py's --sparsity_ratio
+    p.add_argument("--llama_prune_spec", type=str, default=None)
     p.add_argument("--is_global", action="store_true")
     p.add_argument("--sparsity_ratio_granularity", type=str, default=None)
     p.add_argument("--max_sparsity_per_layer", type=float, default=0.8)
@@ -96,7 +99,14 @@ def build_model_and_loader(args, device):
         from .shapes.t5 import T5 as _T5
         from .shapes.unstaged import hide_stage_plan
         hide_stage_plan(Blip2T5, _T5, EVACLIP)
-    if args.shape == "blip2":
+    if args.shape == "llama":
+        from .shapes.llama import llama_7b, llama_batches, llama_tiny
+        with torch.device(device):
+            model = (llama_tiny(dtype=torch.float32 if device.type == "cpu" else torch.float16)
+                     if args.toy else llama_7b())
+        loader = llama_batches(args.num_data, bs, model.seqlen, model.config.vocab_size, seed=args.seed,
+                               device=device)
+    elif args.shape == "blip2":
         from .shapes.blip2_t5 import blip2_flant5xl, blip2_toy
         with torch.device(device):
             model = blip2_toy(fp32=(device.type == "cpu")) if args.toy else blip2_flant5xl()
@@ -240,6 +250,8 @@ def config_dict(args):
         cfg.update(visual_prune_spec=args.visual_prune_spec, language_prune_spec=args.language_prune_spec,
                    language_pruning_method="none", visual_pruning_method="none",
                    language_model_prefix="transformer", visual_model_prefix="visual.transformer")
+    elif str(args.pruning_method).startswith("llama_"):
+        cfg.update(prune_spec=args.llama_prune_spec, model_prefix="model")
     elif str(args.pruning_method).startswith("t5_"):
         cfg.update(prune_spec=args.t5_prune_spec)
     else:

@@ -36,8 +36,9 @@ _f32 = np.float32
 
 def _default_batch_len(batch):
     """Sample count of a calibration batch, as the reference's loss closures report it
-    (pruners/utils.py:29,42: len(samples["text_input"]); :65: len(targets))."""
-    for key in ("text_input", "label", "image"):
+    (pruners/utils.py:29,42: len(samples["text_input"]); :65: len(targets)); a decoder's batch
+    carries "input_ids" alone."""
+    for key in ("text_input", "label", "image", "input_ids"):
         if key in batch:
             return len(batch[key])
     raise ValueError("cannot infer the batch length; pass batch_len_fn")

@@ -2,7 +2,7 @@
 the three the LAVIS pruners use (LAVIS/lavis/compression/pruners/utils.py:21-67: the language
 and vision-language ones read the model's own "loss"; the vision one rebuilds a cross entropy
 from `predict()`'s x100-scaled zero-shot logits) and CoOp's CLIP contrastive closure
-(CoOp/trainers/zsclip.py:73-91)."""
+(CoOp/trainers/zsclip.py:73-91), and the causal LM closure of the LLaMA decoder."""
 import torch
 import torch.nn.functional as F
 
@@ -31,6 +31,14 @@ loss_vision_language = _model_loss("text_input")
 loss_vision_language.__name__ = "loss_vision_language"
 loss_language = _model_loss("text_input")
 loss_language.__name__ = "loss_language"
+
+
+def loss_causal_lm(model, samples, cuda_enabled):
+    """A decoder's own next-token loss on a calibration batch `{"input_ids": [B, T]}`: the labels
+    are the ids themselves (the closure of the reference's LLaMA path lived in a `lib/` its tree does
+    not carry; this is what `LlamaForCausalLM(input_ids, labels=input_ids)` means in transformers)."""
+    ids = _on_model_device(model, samples, cuda_enabled)["input_ids"]
+    return model(ids, labels=ids).loss, len(ids)
 
 
 def loss_vision(model, samples, cuda_enabled):

@@ -448,7 +448,9 @@ class PrefixCachedLoss:
             return self.batch_len_fn(samples)
         if "text_input" in samples:
             return len(samples["text_input"])
-        return len(samples["label"])
+        if "label" in samples:
+            return len(samples["label"])
+        return len(samples["input_ids"])
 
     def _use_family(self, samples):
         """Point `self.chain` (and every lane's) at the graphs of this batch's shape family;

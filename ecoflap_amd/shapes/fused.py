@@ -45,6 +45,7 @@ def _get():
                                                     i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_causal_attention.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
                                                  f32, ci, vp]
+        lib.ecoflap_causal_lm_loss.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, vp]
         lib.ecoflap_multi_copy.argtypes = [vp, ci, vp]
         lib.ecoflap_multi_compare.argtypes = [vp, ci, vp, vp]
         _lib = lib
@@ -294,6 +295,45 @@ def causal_attention(q, k, v, heads, scale, rope=None):
     if rc != 0:
         raise _hip.EcoflapHipError(f"ecoflap_causal_attention failed ({rc})")
     return out
+
+
+def causal_lm_loss(logits, labels, ignore_index=-100, shift=True, return_row_loss=False):
+    """The causal LM loss of transformers' `ForCausalLMLoss` (labels padded by one `ignore_index` and
+    shifted, flat fp32 cross entropy, mean over the rows that have a target) straight from the 16-bit
+    logits [..., T, vocab], read once and in place (`ecoflap_causal_lm_loss`, csrc/lm_loss.hip): no
+    padded or sliced labels, no fp32 copy of the logits.  labels: int64 [..., T]; shift=False takes
+    labels[b, t] as the target of row (b, t).  The last dimension of `logits` has stride 1 and the
+    rows one stride between them (the lm_head's output, or a column slice of a wider buffer).
+    -> the 0-dim fp32 loss (with `return_row_loss`: (loss, fp32 row_loss shaped like `labels`)), or
+    None (caller runs the torch op chain): CPU, autograd, other dtypes, `ECOFLAP_NO_FUSED_LOSS` in
+    the environment, a view the kernel cannot address in place."""
+    import os
+    if (not _usable(logits) or logits.dim() < 2 or logits.numel() == 0 or labels.dtype != torch.int64
+            or labels.device != logits.device or labels.shape != logits.shape[:-1]
+            or os.environ.get("ECOFLAP_NO_FUSED_LOSS")):
+        return None
+    vocab, tokens = logits.shape[-1], logits.shape[-2]
+    rows = labels.numel()
+    stride = logits.stride(-2)
+    if vocab > 1 and logits.stride(-1) != 1:
+        return None
+    # one stride between all rows: every leading dimension steps by whole blocks of rows
+    step = stride * tokens
+    for d in range(logits.dim() - 3, -1, -1):
+        if logits.shape[d] != 1 and logits.stride(d) != step:
+            return None
+        step *= logits.shape[d]
+    lab = labels if labels.is_contiguous() else labels.contiguous()
+    row_loss = torch.empty(labels.shape, dtype=torch.float32, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    rc = _get().ecoflap_causal_lm_loss(logits.data_ptr(), lab.data_ptr(), row_loss.data_ptr(), loss.data_ptr(),
+                                       rows // tokens if tokens else 0, tokens, vocab, stride, int(ignore_index),
+                                       1 if shift else 0, _hip.DTYPE_CODE[logits.dtype], _stream())
+    if rc in (-3, -5):      # ECOFLAP_ESIZE / ECOFLAP_EALIGN: a view the kernel cannot address in place
+        return None
+    if rc != 0:
+        raise _hip.EcoflapHipError(f"ecoflap_causal_lm_loss failed ({rc})")
+    return (loss, row_loss) if return_row_loss else loss
 
 
 def mha_attention_colsq(qkv, heads, scale, out=True, seq_first=True):

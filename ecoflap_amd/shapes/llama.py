@@ -23,10 +23,17 @@ runs `fused.t5_rmsnorm` (LLaMA's RMSNorm is T5's formula), the projections throu
 softmax and both products in one kernel, the projections' outputs read in place), `o_proj`,
 `fused.t5_add_rmsnorm` for residual + post-attention norm, `fused.silu_mul`, `down_proj` and the
 last residual.  Every `None` from a fused op falls back to the torch op at that site alone; the
-kernel serves head width 128 and up to 4096 tokens.
+kernel serves head width 128 and up to 4096 tokens.  There, too, the loss comes from
+`fused.causal_lm_loss` (csrc/lm_loss.hip: the shift is an index inside the kernel and the fp16 logits
+are read once; `ECOFLAP_NO_FUSED_LOSS` in the environment keeps torch's chain).
 
-Not here yet: a LLaMA pruner, `harness --shape llama`, launchers, `stage_plan()`, grouped-query
-attention, a KV cache."""
+`stage_plan()` cuts the forward into `model.embed`, one stage per decoder block and `head` (final
+norm, lm_head, loss) for `PrefixCachedLoss`; `forward` is their composition.  Calibration batches
+are `{"input_ids": LongTensor [B, T]}` and the labels are the ids themselves (`llama_batches`,
+`pruners/losses.py::loss_causal_lm`).
+
+Not here: grouped-query attention, bf16 attention, a KV cache, a tokenizer, datasets, perplexity
+evaluation."""
 from types import SimpleNamespace
 
 import torch
@@ -193,14 +200,58 @@ class LlamaForCausalLM(nn.Module):
             if isinstance(m, (nn.Linear, nn.Embedding)):
                 nn.init.normal_(m.weight, std=cfg.initializer_range)
 
-    def forward(self, input_ids, labels=None):
-        logits = _linear(self.lm_head, self.model(input_ids))
+    def head(self, hidden, labels=None):
+        """lm_head and the loss on the output of `model.norm` -> (logits, loss or None)."""
+        logits = _linear(self.lm_head, hidden)
         loss = None
         if labels is not None:
-            shifted = F.pad(labels, (0, 1), value=-100)[..., 1:].contiguous()
-            loss = F.cross_entropy(logits.float().view(-1, self.config.vocab_size), shifted.view(-1),
-                                   ignore_index=-100, reduction="mean")
-        return SimpleNamespace(logits=logits, loss=loss)
+            if logits.dtype == torch.float16:
+                loss = fused.causal_lm_loss(logits, labels)
+            if loss is None:
+                shifted = F.pad(labels, (0, 1), value=-100)[..., 1:].contiguous()
+                loss = F.cross_entropy(logits.float().view(-1, self.config.vocab_size), shifted.view(-1),
+                                       ignore_index=-100, reduction="mean")
+        return logits, loss
+
+    def _embed_stage(self, batch):
+        if torch.is_tensor(batch):
+            batch = {"input_ids": batch}
+        ids = batch["input_ids"].to(self.lm_head.weight.device)
+        labels = batch.get("labels", ids)
+        return {"x": self.model.embed_tokens(ids),
+                "labels": None if labels is None else labels.to(ids.device)}
+
+    def _head_stage(self, state):
+        logits, loss = self.head(self.model.norm(state["x"]), state["labels"])
+        return {"loss": loss, "logits": logits}
+
+    def stage_plan(self):
+        """[(name, owned parameter prefixes, fn(state) -> state)]; stage 0 takes the batch
+        `{"input_ids": [B, T]}` (labels: the ids unless the batch carries "labels"), a block stage
+        maps {"x", "labels"} to itself and `head` returns {"loss", "logits"}."""
+        def block(layer):
+            return lambda state: {"x": layer(state["x"]), "labels": state["labels"]}
+        return ([("model.embed", ["model.embed_tokens."], self._embed_stage)]
+                + [(f"model.layers.{i}", [f"model.layers.{i}."], block(layer))
+                   for i, layer in enumerate(self.model.layers)]
+                + [("head", ["model.norm.", "lm_head."], self._head_stage)])
+
+    def forward(self, input_ids, labels=None):
+        state = {"input_ids": input_ids, "labels": labels}
+        for _, _, fn in self.stage_plan():
+            state = fn(state)
+        return SimpleNamespace(logits=state["logits"], loss=state["loss"])
+
+
+def llama_batches(n, batch_size, seqlen, vocab, seed=0, device=None):
+    """n seeded calibration batches `{"input_ids": LongTensor [batch_size, seqlen]}`; a causal LM's
+    labels are its input ids."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for _ in range(n):
+        ids = torch.randint(0, vocab, (batch_size, seqlen), generator=g)
+        out.append({"input_ids": ids if device is None else ids.to(device)})
+    return out
 
 
 def llama_config(hidden_size, heads, intermediate_size, layers, vocab_size, head_dim=None,

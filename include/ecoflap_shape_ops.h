@@ -150,6 +150,33 @@ int ecoflap_causal_attention(const void* q, const void* k, const void* v, void* 
                              int64_t out_token_stride, int64_t out_batch_stride, float scale,
                              int dtype, void* stream);
 
+/* The causal language-model loss of a decoder, from the 16-bit logits its lm_head wrote
+ * (transformers' ForCausalLMLoss: labels padded by one ignore_index and shifted, flat fp32 cross
+ * entropy, mean; csrc/lm_loss.hip).  logits: [batch * tokens, vocab] of F16 / BF16, row r at
+ * logits + r * logits_row_stride elements (the lm_head output, or a column slice of a wider buffer,
+ * read in place); labels: [batch, tokens] int64, contiguous.  shift = 1: the target of row (b, t) is
+ * labels[b, t + 1] and the last token of every sample has none; shift = 0: labels[b, t].
+ *   row_loss[r] = -log_softmax(float(logits[r]))[target] in fp32 (maximum, sum(exp(x - max)) and
+ *     the target's logit in fp32, nll = log(sum) + max - x_target); exactly 0 where the row has no
+ *     target or the target equals ignore_index (such a row is not read).  [batch * tokens], caller-owned.
+ *   loss_out[0] = (sum of row_loss over the rows with a target) / (their number); NaN when there is
+ *     none, as F.cross_entropy(reduction="mean") answers.
+ * A target that is neither ignore_index nor in [0, vocab) makes its row's loss and the mean NaN
+ * (torch raises a device-side assert there); nothing outside [0, vocab) of any row is ever read,
+ * whatever the labels hold.  Every logit is read once, in 16-byte vectors (a ragged tail of vocab % 8
+ * elements one by one); any vocab >= 1.  The mean is a second one-workgroup launch adding row_loss in
+ * fp64 in an order fixed by batch * tokens alone: no atomics, the same bits on every call, and a
+ * row's loss does not depend on the other rows (batch invariant bit for bit).  Launches only (no
+ * synchronisation, no allocation, no host read of labels): usable inside a captured graph.
+ * ECOFLAP_ENULL: a null logits, labels, row_loss or loss_out; ECOFLAP_EDTYPE: not F16 / BF16;
+ * ECOFLAP_ESIZE: batch, tokens or vocab < 0, vocab == 0 with rows, logits_row_stride < vocab, or
+ * batch * tokens >= 2^31; ECOFLAP_EMODE: shift not 0 or 1; ECOFLAP_EALIGN: logits not 16-byte
+ * aligned, logits_row_stride % 8 != 0, or labels / row_loss / loss_out not aligned to their element.
+ * Nothing is launched on an error.  batch * tokens == 0: returns 0, loss_out[0] = NaN, nothing read. */
+int ecoflap_causal_lm_loss(const void* logits, const int64_t* labels, float* row_loss, float* loss_out,
+                           int64_t batch, int64_t tokens, int64_t vocab, int64_t logits_row_stride,
+                           int64_t ignore_index, int shift, int dtype, void* stream);
+
 /* Up to ECOFLAP_COPY_MAX_ITEMS device-to-device copies (non-overlapping, any alignment) in
  * one launch: the loop's state hand-overs between static graph buffers. */
 #define ECOFLAP_COPY_MAX_ITEMS 32
