@@ -5,21 +5,25 @@
 The model is the random-init decoder of that shape and the calibration ids are synthetic; the
 perplexity evaluation behind the pruning is the model zoo's and is not reproduced.
 
-    python LLaMA/scripts/ecoflap_zero.py [extra harness flags]
+    python LLaMA/scripts/ecoflap_zero.py [--prune_method {wanda,sparsegpt}] [extra harness flags]
+
+`--prune_method sparsegpt` (LLaMA/main.py:36) runs `llama_sparsegpt_pruner` on the same table and
+writes under out/llama_7b/unstructured/ecoflap_zero_sparsegpt0.6/.
 
 Outputs go under out/llama_7b/unstructured/ecoflap_zero0.6/ with --save_pruned_model."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _llama_launch import harness_flags, run  # noqa: E402
+from _llama_launch import harness_flags, run, split_args  # noqa: E402
 
 NUM_SAMPLES_FOR_FIRST_STAGE = 32
 
 
-def flags():
-    return harness_flags("ecoflap_zero", "MEZO-GradOnly_sum", NUM_SAMPLES_FOR_FIRST_STAGE)
+def flags(prune_method="wanda"):
+    return harness_flags("ecoflap_zero", "MEZO-GradOnly_sum", NUM_SAMPLES_FOR_FIRST_STAGE, prune_method=prune_method)
 
 
 if __name__ == "__main__":
-    sys.exit(run(flags(), sys.argv[1:]))
+    method, extra = split_args(sys.argv[1:])
+    sys.exit(run(flags(method), extra))

@@ -25,6 +25,9 @@
 // below, an fp32 MFMA kernel of this file, and `ecoflap_sparsegpt_matrix` queues the whole column
 // sweep of one Linear — widen, every block step, every trailing update, round back — from one
 // host call (CoOp/trainers/pruners/sparsegpt_pruner.py:176-189, :261-307).
+// `ecoflap_sparsegpt_matrix_group` does the same for up to 8 Linears that share Hinv (q / k / v,
+// gate / up of a decoder block) with the launches of ONE matrix per column block: the histogram and
+// sweep bodies below are shared by the single and the grouped kernels.
 #include "common.h"
 
 struct SgptSelState {
@@ -85,11 +88,12 @@ static __device__ __forceinline__ uint32_t sg_metric_bits(float w, float d) {
     return __float_as_uint(a / b);
 }
 
+// one histogram pass over W[rows, i1:i1+count) into st->hist[PASS]; the whole workgroup calls it
 template <int PASS>
-__global__ __launch_bounds__(256) void sgpt_hist_kernel(const float* __restrict__ W, int64_t rows,
-                                                        int64_t ldw, const float* __restrict__ Hinv,
-                                                        int64_t ldh, int64_t i1, int count,
-                                                        uint32_t rank0, SgptSelState* st) {
+static __device__ __forceinline__ void sg_hist_pass(const float* __restrict__ W, int64_t rows,
+                                                    int64_t ldw, const float* __restrict__ Hinv,
+                                                    int64_t ldh, int64_t i1, int count,
+                                                    uint32_t rank0, SgptSelState* st) {
     constexpr int SHIFT = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0);
     constexpr int BITS = PASS == 2 ? 10 : 11;
     constexpr uint32_t HI_MASK = PASS == 0 ? 0u : (PASS == 1 ? 0xffe00000u : 0xfffffc00u);
@@ -114,14 +118,53 @@ __global__ __launch_bounds__(256) void sgpt_hist_kernel(const float* __restrict_
         if (h[i]) atomicAdd(&st->hist[PASS][i], h[i]);
 }
 
-// one wave per row; workgroup = 4 rows sharing Hinv1 in LDS
-__global__ __launch_bounds__(256) void sgpt_sweep_kernel(float* W, int64_t rows, int64_t ldw,
-                                                         const float* __restrict__ Hinv, int64_t ldh,
-                                                         int64_t i1, int count, uint32_t rank0,
-                                                         const SgptSelState* st, int use_thresh,
-                                                         const uint8_t* __restrict__ mask_in,
-                                                         float* __restrict__ Err, uint8_t* mask_out,
-                                                         int nm_n, int nm_m) {
+template <int PASS>
+__global__ __launch_bounds__(256) void sgpt_hist_kernel(const float* __restrict__ W, int64_t rows,
+                                                        int64_t ldw, const float* __restrict__ Hinv,
+                                                        int64_t ldh, int64_t i1, int count,
+                                                        uint32_t rank0, SgptSelState* st) {
+    sg_hist_pass<PASS>(W, rows, ldw, Hinv, ldh, i1, count, rank0, st);
+}
+
+// ---- the members of a grouped sweep (`ecoflap_sparsegpt_matrix_group`) ---------------------------
+// Member g owns rows [off[g], off[g] + rows[g]) of the stacked fp32 working copy and of Err; every
+// off[g] is a multiple of SGT_WG_ROWS, so a sweep workgroup never holds rows of two members; the
+// rows between a member's last row and the next offset are padding (zero in the working copy, never
+// counted into a histogram, never written back).  Passed by value; read with constant indices only
+// (a dynamic index into kernel arguments would go through scratch).
+#define SGPT_MAX_GROUP ECOFLAP_SGPT_MAX_GROUP
+#define SGT_WG_ROWS 4
+struct SgptGroup {
+    int64_t off[SGPT_MAX_GROUP];
+    int64_t rows[SGPT_MAX_GROUP];
+    uint32_t rank0[SGPT_MAX_GROUP];
+    int n;
+};
+
+// grid (x, n members): member blockIdx.y's elements are counted into ITS state st[blockIdx.y] only
+template <int PASS>
+__global__ __launch_bounds__(256) void sgpt_hist_group_kernel(const float* __restrict__ W, int64_t ldw,
+                                                              const float* __restrict__ Hinv, int64_t ldh,
+                                                              int64_t i1, int count, SgptGroup grp,
+                                                              SgptSelState* st) {
+    int64_t off = grp.off[0], rows = grp.rows[0];
+    uint32_t rank0 = grp.rank0[0];
+#pragma unroll
+    for (int k = 1; k < SGPT_MAX_GROUP; ++k)
+        if (k == (int)blockIdx.y) { off = grp.off[k]; rows = grp.rows[k]; rank0 = grp.rank0[k]; }
+    sg_hist_pass<PASS>(W + off * ldw, rows, ldw, Hinv, ldh, i1, count, rank0, st + blockIdx.y);
+}
+
+// one wave per row; workgroup = 4 rows sharing Hinv1 in LDS.  The whole workgroup calls this with
+// ONE (rank0, st) — it resolves the threshold behind barriers; `row` is the wave's row of W and Err,
+// `live` false for a wave without a row (it leaves after the barriers).
+static __device__ __forceinline__ void sg_sweep_rows(float* W, int64_t ldw,
+                                                     const float* __restrict__ Hinv, int64_t ldh,
+                                                     int64_t i1, int count, uint32_t rank0,
+                                                     const SgptSelState* st, int use_thresh,
+                                                     const uint8_t* __restrict__ mask_in,
+                                                     float* __restrict__ Err, uint8_t* mask_out,
+                                                     int nm_n, int nm_m, int64_t row, bool live) {
     // upper triangle of Hinv1, packed: row i starts at i*count - i*(i-1)/2, holds j = i..count-1
     extern __shared__ __attribute__((aligned(16))) float Hs[];
     __shared__ uint32_t wave4[4];
@@ -136,8 +179,7 @@ __global__ __launch_bounds__(256) void sgpt_sweep_kernel(float* W, int64_t rows,
     __syncthreads();
     const float thresh = __uint_as_float(thres_bits);
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
+    if (!live) return;
     float* wrow = W + row * ldw + i1;
     float w[2], q[2] = {0.f, 0.f}, er[2] = {0.f, 0.f};
     bool mk[2];
@@ -211,6 +253,44 @@ __global__ __launch_bounds__(256) void sgpt_sweep_kernel(float* W, int64_t rows,
             Err[row * count + j] = er[t];
             if (mask_out) mask_out[row * count + j] = mk[t] ? 1 : 0;
         }
+    }
+#undef HS
+}
+
+__global__ __launch_bounds__(256) void sgpt_sweep_kernel(float* W, int64_t rows, int64_t ldw,
+                                                         const float* __restrict__ Hinv, int64_t ldh,
+                                                         int64_t i1, int count, uint32_t rank0,
+                                                         const SgptSelState* st, int use_thresh,
+                                                         const uint8_t* __restrict__ mask_in,
+                                                         float* __restrict__ Err, uint8_t* mask_out,
+                                                         int nm_n, int nm_m) {
+    const int64_t row = (int64_t)blockIdx.x * SGT_WG_ROWS + (threadIdx.x >> 6);
+    sg_sweep_rows(W, ldw, Hinv, ldh, i1, count, rank0, st, use_thresh, mask_in, Err, mask_out, nm_n,
+                  nm_m, row, row < rows);
+}
+
+// The sweep over the stacked rows of a group: the workgroup's four rows lie in ONE member (offsets
+// are multiples of four), whose rank and state it resolves; a padding row gets Err = 0, so the
+// trailing update leaves its zeros alone.
+__global__ __launch_bounds__(256) void sgpt_sweep_group_kernel(float* W, int64_t ldw,
+                                                               const float* __restrict__ Hinv, int64_t ldh,
+                                                               int64_t i1, int count, SgptGroup grp,
+                                                               const SgptSelState* st, int use_thresh,
+                                                               float* __restrict__ Err, int nm_n, int nm_m) {
+    const int64_t row0 = (int64_t)blockIdx.x * SGT_WG_ROWS;
+    int64_t off = grp.off[0], rows = grp.rows[0];
+    uint32_t rank0 = grp.rank0[0];
+    int g = 0;
+#pragma unroll
+    for (int k = 1; k < SGPT_MAX_GROUP; ++k)
+        if (k < grp.n && row0 >= grp.off[k]) { g = k; off = grp.off[k]; rows = grp.rows[k]; rank0 = grp.rank0[k]; }
+    const int64_t row = row0 + (threadIdx.x >> 6);
+    const bool live = row - off < rows;
+    sg_sweep_rows(W, ldw, Hinv, ldh, i1, count, rank0, st + g, use_thresh, (const uint8_t*)nullptr, Err,
+                  (uint8_t*)nullptr, nm_n, nm_m, row, live);
+    if (!live) {
+        const int lane = threadIdx.x & 63;
+        for (int j = lane; j < count; j += 64) Err[row * count + j] = 0.f;
     }
 }
 
@@ -552,4 +632,140 @@ extern "C" int ecoflap_sparsegpt_matrix(void* w, int dtype, int64_t rows, int64_
         }
     }
     return sgpt_convert(false, dtype, w, W32, rows, cols, nullptr, s);
+}
+
+// ---- the whole sweep of up to 8 Linears that share Hinv, from one host call ----------------------
+// (q / k / v, gate / up of a decoder block: the same input, so the same H and the same factor.)
+// The members' fp32 working copies are stacked into one [R, cols] matrix, member g at row off[g], a
+// multiple of SGT_WG_ROWS; Err is stacked the same way.  Rows are independent in every step, and the
+// trailing kernel's bits do not depend on where a row lies in the grid, so a column block costs the
+// launches of ONE matrix — a clear, three histogram passes with a member dimension in the grid (a
+// state, a rank and a histogram per member), one sweep, one trailing update over all R rows —
+// however many members there are, and every member ends with the bits of its own
+// `ecoflap_sparsegpt_matrix` call.
+static int64_t sg_group_pad(int64_t rows) { return (rows + SGT_WG_ROWS - 1) / SGT_WG_ROWS * SGT_WG_ROWS; }
+
+// per-member size checks of the single entry; -> stacked (padded) row count in *total
+static int sgpt_group_rows(const ecoflap_sgpt_group_item* items, int n_items, int64_t cols, int64_t* total) {
+    if (!items) return ECOFLAP_ENULL;
+    if (n_items <= 0 || n_items > SGPT_MAX_GROUP || cols <= 0) return ECOFLAP_ESIZE;
+    int64_t R = 0;
+    for (int g = 0; g < n_items; ++g) {
+        if (items[g].rows <= 0 || items[g].rows > ((int64_t)1 << 40) / cols) return ECOFLAP_ESIZE;
+        R += sg_group_pad(items[g].rows);
+    }
+    *total = R;
+    return 0;
+}
+
+// workspace of `ecoflap_sparsegpt_matrix_group`: the stacked working copy [R, cols], Err [R, 128] and
+// one selection state per member, each on a 256-byte boundary (0 for what the entry refuses)
+extern "C" size_t ecoflap_sparsegpt_matrix_group_workspace_bytes(const ecoflap_sgpt_group_item* items,
+                                                                 int n_items, int64_t cols) {
+    int64_t R;
+    if (sgpt_group_rows(items, n_items, cols, &R)) return 0;
+    return sg_align256((size_t)R * (size_t)cols * 4) + sg_align256((size_t)R * 128 * 4) +
+           sg_align256((size_t)n_items * sizeof(SgptSelState));
+}
+
+extern "C" int ecoflap_sparsegpt_matrix_group(const ecoflap_sgpt_group_item* items, int n_items, int dtype,
+                                              int64_t cols, const float* Hinv, int64_t ldh,
+                                              const uint8_t* dead, int blocksize, int prune_n, int prune_m,
+                                              void* workspace, size_t workspace_bytes, void* stream,
+                                              int64_t* launches_out) {
+    if (!dtype_ok(dtype)) return ECOFLAP_EDTYPE;
+    if (!items) return ECOFLAP_ENULL;
+    if (n_items <= 0 || n_items > SGPT_MAX_GROUP) return ECOFLAP_ESIZE;
+    if (cols <= 0 || blocksize <= 0 || blocksize > 128 || ldh < cols) return ECOFLAP_ESIZE;
+    int64_t R;
+    int rc = sgpt_group_rows(items, n_items, cols, &R);
+    if (rc) return rc;
+    if (!Hinv || !workspace) return ECOFLAP_ENULL;
+    for (int g = 0; g < n_items; ++g)
+        if (!items[g].w || (prune_n == 0 && !items[g].ranks_host)) return ECOFLAP_ENULL;
+    if (prune_n < 0 || (prune_n == 0 && prune_m != 0)) return ECOFLAP_ESIZE;
+    // every member against the single entry's checks (its own rows, its own ranks), then the grids
+    // that span the stack
+    for (int g = 0; g < n_items; ++g)
+        for (int64_t i1 = 0, b = 0; i1 < cols; i1 += blocksize, ++b) {
+            const int count = (int)(cols - i1 < blocksize ? cols - i1 : blocksize);
+            rc = sgpt_block_check(items[g].rows, cols, ldh, i1, count, prune_n ? 0 : items[g].ranks_host[b],
+                                  prune_n == 0);
+            if (rc == 0 && prune_n) rc = sgpt_nm_check(count, prune_n, prune_m);
+            if (rc == 0 && i1 + count < cols)
+                rc = sgpt_trailing_check(items[g].rows, cols, cols, ldh, i1, count, i1 + count);
+            if (rc) return rc;
+        }
+    if (R / SGT_WG_ROWS > 0x7fffffffLL) return ECOFLAP_ESIZE;
+    if (cols > blocksize && (rc = sgpt_trailing_check(R, cols, cols, ldh, 0, blocksize, blocksize)) != 0) return rc;
+    if (workspace_bytes < ecoflap_sparsegpt_matrix_group_workspace_bytes(items, n_items, cols))
+        return ECOFLAP_EWORKSPACE;
+    if (!aligned16(workspace)) return ECOFLAP_EALIGN;
+
+    hipStream_t s = (hipStream_t)stream;
+    float* W32 = (float*)workspace;
+    float* Err = (float*)((char*)workspace + sg_align256((size_t)R * (size_t)cols * 4));
+    SgptSelState* st = (SgptSelState*)((char*)Err + sg_align256((size_t)R * 128 * 4));
+    int64_t launches[5] = {0, 0, 0, 0, 0};      // clears, histogram, sweep, trailing, widen + narrow
+    SgptGroup grp;
+    grp.n = n_items;
+    int64_t hist_blocks = 1;
+    for (int64_t g = 0, at = 0; g < SGPT_MAX_GROUP; ++g) {
+        grp.off[g] = grp.rows[g] = 0;
+        grp.rank0[g] = 0;
+        if (g >= n_items) continue;
+        grp.off[g] = at;
+        grp.rows[g] = items[g].rows;
+        at += sg_group_pad(items[g].rows);
+        // the single entry's histogram grid at a full block, per member: the widest is launched for
+        // all (the counts are integer atomics: they do not depend on the grid)
+        int64_t b = (items[g].rows * (cols < blocksize ? cols : (int64_t)blocksize) + 256 * 8 - 1) / (256 * 8);
+        if (b > 512) b = 512;
+        if (b > hist_blocks) hist_blocks = b;
+    }
+    for (int g = 0; g < n_items; ++g) {
+        float* Wg = W32 + grp.off[g] * cols;
+        rc = sgpt_convert(true, dtype, items[g].w, Wg, items[g].rows, cols, dead, s);
+        if (rc) return rc;
+        ++launches[4];
+        const int64_t pad = sg_group_pad(items[g].rows) - items[g].rows;
+        if (pad) {      // padding rows: zero, and they stay zero (the sweep gives them Err = 0)
+            hipError_t e = hipMemsetAsync(Wg + items[g].rows * cols, 0, (size_t)pad * (size_t)cols * 4, s);
+            if (e != hipSuccess) return (int)e;
+        }
+    }
+    const dim3 blk(256);
+    for (int64_t i1 = 0, b = 0; i1 < cols; i1 += blocksize, ++b) {
+        const int count = (int)(cols - i1 < blocksize ? cols - i1 : blocksize);
+        if (prune_n == 0) {
+            for (int g = 0; g < n_items; ++g) grp.rank0[g] = (uint32_t)(items[g].ranks_host[b] + 1);
+            hipError_t e = hipMemsetAsync(st, 0, (size_t)n_items * sizeof(SgptSelState), s);
+            if (e != hipSuccess) return (int)e;
+            ++launches[0];
+            const dim3 grid((unsigned)hist_blocks, (unsigned)n_items);
+            hipLaunchKernelGGL((sgpt_hist_group_kernel<0>), grid, blk, 0, s, W32, cols, Hinv, ldh, i1, count, grp, st);
+            hipLaunchKernelGGL((sgpt_hist_group_kernel<1>), grid, blk, 0, s, W32, cols, Hinv, ldh, i1, count, grp, st);
+            hipLaunchKernelGGL((sgpt_hist_group_kernel<2>), grid, blk, 0, s, W32, cols, Hinv, ldh, i1, count, grp, st);
+            ECO_CHECK_LAUNCH();
+            launches[1] += 3;
+        }
+        const size_t lds = ((size_t)count * (count + 1) / 2) * sizeof(float);
+        hipLaunchKernelGGL(sgpt_sweep_group_kernel, dim3((unsigned)(R / SGT_WG_ROWS)), blk, lds, s, W32, cols,
+                           Hinv, ldh, i1, count, grp, st, prune_n == 0 ? 1 : 0, Err, prune_n, prune_m);
+        ECO_CHECK_LAUNCH();
+        ++launches[2];
+        if (i1 + count < cols) {
+            rc = sgpt_trailing_launch(W32, R, cols, cols, Err, Hinv, ldh, i1, count, i1 + count, s);
+            if (rc) return rc;
+            ++launches[3];
+        }
+    }
+    for (int g = 0; g < n_items; ++g) {
+        rc = sgpt_convert(false, dtype, items[g].w, W32 + grp.off[g] * cols, items[g].rows, cols, nullptr, s);
+        if (rc) return rc;
+        ++launches[4];
+    }
+    if (launches_out)
+        for (int i = 0; i < 5; ++i) launches_out[i] = launches[i];
+    return 0;
 }

@@ -35,6 +35,7 @@ EXPORTS = [
     "ecoflap_mask_mul", "ecoflap_allocate_sparsity",
     "ecoflap_sparsegpt_workspace_bytes", "ecoflap_sparsegpt_block", "ecoflap_sparsegpt_block_nm",
     "ecoflap_sparsegpt_trailing", "ecoflap_sparsegpt_matrix_workspace_bytes", "ecoflap_sparsegpt_matrix",
+    "ecoflap_sparsegpt_matrix_group_workspace_bytes", "ecoflap_sparsegpt_matrix_group",
     "ecoflap_hessian_workspace_bytes", "ecoflap_hessian_accum", "ecoflap_cholesky_workspace_bytes", "ecoflap_cholesky_f32",
     "ecoflap_cholesky_inverse_workspace_bytes", "ecoflap_cholesky_inverse_f32",
     "ecoflap_grad_accum_multi", "ecoflap_global_prune_workspace_bytes",
@@ -61,6 +62,14 @@ class ColsqItem(ctypes.Structure):
                 ("nsamples_before", ctypes.c_int64), ("nsamples_dev", ctypes.c_void_p),
                 ("batch", ctypes.c_int64), ("raw", ctypes.c_int)]
 
+
+class SgptGroupItem(ctypes.Structure):
+    """`ecoflap_sgpt_group_item` (include/ecoflap_hip.h)."""
+    _fields_ = [("w", ctypes.c_void_p), ("rows", ctypes.c_int64), ("ranks_host", ctypes.c_void_p)]
+
+
+SGPT_MAX_GROUP = 8
+SGPT_GROUP_LAUNCH_KINDS = ("state_clears", "histogram", "sweep", "trailing", "convert")
 
 COLSQ_MAX_ITEMS = 16
 _COLSQ_BYTES = ctypes.sizeof(ColsqItem)
@@ -161,6 +170,9 @@ def load_library():
     lib.ecoflap_sparsegpt_matrix_workspace_bytes.restype = sz
     lib.ecoflap_sparsegpt_matrix_workspace_bytes.argtypes = [i64, i64]
     lib.ecoflap_sparsegpt_matrix.argtypes = [vp, ci, i64, i64, vp, i64, vp, ci, vp, ci, ci, vp, sz, vp]
+    lib.ecoflap_sparsegpt_matrix_group_workspace_bytes.restype = sz
+    lib.ecoflap_sparsegpt_matrix_group_workspace_bytes.argtypes = [vp, ci, i64]
+    lib.ecoflap_sparsegpt_matrix_group.argtypes = [vp, ci, ci, i64, vp, i64, vp, ci, ci, ci, vp, sz, vp, vp]
     lib.ecoflap_hessian_workspace_bytes.restype = sz
     lib.ecoflap_hessian_workspace_bytes.argtypes = [i64, i64]
     lib.ecoflap_hessian_accum.argtypes = [vp, vp, i64, i64, ci, i64, i64, vp, sz, vp]
@@ -850,6 +862,54 @@ class HipKernels:
             _ptr(w), DTYPE_CODE[w.dtype], rows, cols, _ptr(Hinv), Hinv.stride(0), _ptr(dead),
             int(blocksize), ranks_a, int(prune_n), int(prune_m), _ptr(ws), ws.numel(), _stream()),
             "ecoflap_sparsegpt_matrix")
+
+    def sparsegpt_matrix_group(self, ws, Hinv, dead, blocksize, ranks_per_member, prune_n=0, prune_m=0):
+        """`sparsegpt_matrix` for up to 8 weights `ws` that share `Hinv` and `dead` (Linears fed by the
+        same tensor) in ONE host call whose launches per column block do not grow with len(ws); every
+        weight ends with the bits of its own `sparsegpt_matrix` call.  ranks_per_member: per weight
+        one python int per column block (None under n:m).  -> what was queued, by
+        SGPT_GROUP_LAUNCH_KINDS."""
+        _gpu(Hinv, "Hinv")
+        if not 0 < len(ws) <= SGPT_MAX_GROUP:
+            raise EcoflapHipError(f"sparsegpt_matrix_group: 1 to {SGPT_MAX_GROUP} weights")
+        w0 = ws[0]
+        for w in ws:
+            _gpu(w, "w")
+            if (w.dim() != 2 or w.dtype not in DTYPE_CODE or w.dtype != w0.dtype or w.shape[1] != w0.shape[1]
+                    or w.device != w0.device or not w.is_contiguous()):
+                raise EcoflapHipError("sparsegpt_matrix_group: contiguous 2-D fp16 / bf16 / fp32 weights of one "
+                                      "dtype, column count and device")
+        if Hinv.dtype != torch.float32:
+            raise EcoflapHipError("sparsegpt_matrix_group: an fp32 Hinv")
+        cols = w0.shape[1]
+        if dead is not None:
+            if isinstance(dead, torch.Tensor) and dead.dtype == torch.bool:
+                dead = dead.view(torch.uint8)
+            _gpu(dead, "dead")
+            if dead.dtype != torch.uint8 or dead.numel() != cols:
+                raise EcoflapHipError("dead must be bool / uint8 [cols]")
+        n_blocks = -(-cols // int(blocksize)) if blocksize > 0 else 0
+        if ranks_per_member is None:
+            ranks_per_member = [None] * len(ws)
+        if len(ranks_per_member) != len(ws):
+            raise EcoflapHipError("sparsegpt_matrix_group: one list of ranks per weight")
+        items = (SgptGroupItem * len(ws))()
+        keep = []                                   # the host rank arrays live until the call returns
+        for it, w, ranks in zip(items, ws, ranks_per_member):
+            it.w, it.rows, it.ranks_host = w.data_ptr(), w.shape[0], None
+            if ranks is not None:
+                if len(ranks) != n_blocks:
+                    raise EcoflapHipError("sparsegpt_matrix_group: one rank per column block")
+                keep.append((ctypes.c_int64 * n_blocks)(*[int(k) for k in ranks]))
+                it.ranks_host = ctypes.cast(keep[-1], ctypes.c_void_p)
+        nb = self.lib.ecoflap_sparsegpt_matrix_group_workspace_bytes(ctypes.byref(items), len(ws), cols)
+        buf = self.sgpt_ws.get(nb, w0.device)
+        launches = (ctypes.c_int64 * len(SGPT_GROUP_LAUNCH_KINDS))()
+        _check(self.lib.ecoflap_sparsegpt_matrix_group(
+            ctypes.byref(items), len(ws), DTYPE_CODE[w0.dtype], cols, _ptr(Hinv), Hinv.stride(0), _ptr(dead),
+            int(blocksize), int(prune_n), int(prune_m), _ptr(buf), buf.numel(), _stream(), launches),
+            "ecoflap_sparsegpt_matrix_group")
+        return dict(zip(SGPT_GROUP_LAUNCH_KINDS, launches))
 
     # ---- K8 ---------------------------------------------------------------------------
     def cholesky(self, H, upper=False):

@@ -81,3 +81,30 @@ class LlamaLayerWandaPruner(_StageOneMixin, LayerWiseBasePruner):
                                  n_samples=self.num_samples, sparsity_ratio=sparsity_dict)
         self.model_reset(self.model, dtype_record, requires_grad_record, device)
         return self.model, sparsity_dict
+
+
+@registry.register_pruner("llama_sparsegpt_pruner")
+class LlamaLayerSparseGPTPruner(LlamaLayerWandaPruner):
+    """ECoFLaP / SparseGPT on the same decoder (`LLaMA/main.py:36`, `--prune_method sparsegpt`): stage 1,
+    `get_sparsity` and `prune()` are `llama_wanda_pruner`'s; stage 2 is `_BlockwiseWanda`'s SparseGPT
+    branch — per block one hooked pass completes the seven Hessians, then every matrix is swept at
+    its table entry (the loop of `T5LayerSparseGPTPruner._prune`, sparsegpt_pruner.py:226-420, which
+    the CPU run equals bit for bit).  q / k / v and gate / up see the same tensor: their Hessians are
+    bit-identical, one factorisation serves each set, and with `sparsegpt_group_twins` each set's
+    sweeps run side by side in one host call (`ecoflap_sparsegpt_matrix_group`), every matrix with the
+    bits of its own sweep."""
+    pruner_name = "llama_sparsegpt_pruner"
+    local_method = "sparsegpt"
+    whole_matrix_sweep = True       # the column sweep of a matrix in one host call (pruners/sparsegpt.py)
+    literal_update = True           # fp32 inputs: `H += x^T x` as the reference rounds it
+    # Twin sets swept side by side: on, by the measurement at the 7B shapes (DESIGN §9: the grouped
+    # median is below the one-by-one median by more than the one-by-one form's own max - min at
+    # 3 x [4096, 4096] and at 2 x [11008, 4096]); the bits are those of the one-by-one sweeps.
+    sparsegpt_group_twins = True
+
+    def __init__(self, model, data_loader, whole_matrix_sweep=None, sparsegpt_group_twins=None, **kwargs):
+        super().__init__(model, data_loader, **kwargs)
+        if whole_matrix_sweep is not None:
+            self.whole_matrix_sweep = bool(whole_matrix_sweep)
+        if sparsegpt_group_twins is not None:
+            self.sparsegpt_group_twins = bool(sparsegpt_group_twins)

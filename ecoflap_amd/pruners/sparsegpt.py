@@ -14,7 +14,9 @@ torch runs as ~1000 small kernels per 128 columns, is one fused HIP step
 (`ecoflap_sparsegpt_block`, csrc/sparsegpt.hip).  With `SparseGPT.whole_matrix_sweep` (off by
 default; `clip_sparsegpt_pruner` turns it on) the whole sweep of a Linear — the fp32 copy, every
 block step, every trailing update on an fp32 MFMA kernel of the build, the cast back — is ONE host
-call (`ecoflap_sparsegpt_matrix`).
+call (`ecoflap_sparsegpt_matrix`), and `SparseGPT.sweep_group` sweeps Linears that share one factor
+(twins: the same input) side by side in one call (`ecoflap_sparsegpt_matrix_group`;
+`llama_sparsegpt_pruner`).
 """
 import math
 
@@ -81,7 +83,7 @@ class SparseGPT:
     # its own, then added.  `addmm_` hands H to the GEMM as its accumulator, and a library that
     # blocks over k then rounds in another order (a CPU GEMM does above a few hundred tokens).
     # The pruners that came first keep `addmm_` and their recorded hashes; `clip_sparsegpt_pruner`
-    # sets this on its own objects.
+    # and `llama_sparsegpt_pruner` set this on their own objects.
     literal_update = False
 
     def flush(self):
@@ -249,6 +251,44 @@ class SparseGPT:
                      for i1 in range(0, self.columns, blocksize)]
         with PhaseTimer.span("sparsegpt.sweep (one call: csrc/sparsegpt.hip)"):
             self.kernels.sparsegpt_matrix(self.layer.weight.data, Hinv, dead, blocksize, ranks, prune_n, prune_m)
+
+    @classmethod
+    def sweep_group(cls, objects, sparsities, prune_n=0, prune_m=0, blocksize=128, percdamp=.01):
+        """`fasterprune` of Linears that saw the very same inputs (q / k / v, gate / up: bit-identical
+        H, checked by the caller), each at its own sparsity, sharing the factor of `objects[0]`.
+        Where the one-call sweep applies to all of them and their weights have one dtype, column
+        count and device, the sweeps run side by side in ONE host call
+        (`ecoflap_sparsegpt_matrix_group`: per column block the launches of one matrix, every weight
+        with the bits of its own sweep) -> True; otherwise one `fasterprune` each -> False."""
+        first = objects[0]
+        w0 = first.layer.weight.data
+        grouped = (1 < len(objects) <= _hip.SGPT_MAX_GROUP
+                   and hasattr(first.kernels, "sparsegpt_matrix_group")
+                   and all(o._one_call_sweep_applies(blocksize) and o.kernels is first.kernels
+                           and o.layer.weight.data.dtype == w0.dtype and o.columns == first.columns
+                           and o.layer.weight.data.device == w0.device for o in objects))
+        if not grouped:
+            for i, (o, sparsity) in enumerate(zip(objects, sparsities)):
+                o.fasterprune(sparsity, prune_n=prune_n, prune_m=prune_m, blocksize=blocksize, percdamp=percdamp,
+                              same_hessian_as=first if i else None)
+            return False
+        for o in objects:
+            o.flush()
+        if first.factor is None:
+            with PhaseTimer.span("sparsegpt.factor (clamp, 2 damped Cholesky, inverse: csrc/cholesky.hip)"):
+                first._factor_alone(percdamp)
+        dead, Hinv = first.factor
+        ranks = None
+        if prune_n == 0:                                   # int(tmp.numel() * sparsity) (:187), per member
+            ranks = [[int(o.rows * (min(i1 + blocksize, o.columns) - i1) * sparsity)
+                      for i1 in range(0, o.columns, blocksize)] for o, sparsity in zip(objects, sparsities)]
+        for o in objects:
+            o.H = None
+            o.factor = first.factor
+        with PhaseTimer.span("sparsegpt.sweep (one call per twin set: csrc/sparsegpt.hip)"):
+            first.kernels.sparsegpt_matrix_group([o.layer.weight.data for o in objects], Hinv, dead, blocksize,
+                                                 ranks, prune_n, prune_m)
+        return True
 
     def fasterprune(self, sparsity, prune_n=0, prune_m=0, blocksize=128, percdamp=.01,
                     same_hessian_as=None):

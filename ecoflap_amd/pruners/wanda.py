@@ -730,6 +730,10 @@ class _BlockwiseWanda:
             if sparsegpt:
                 from .sparsegpt import SparseGPT
                 wrapped = {name: SparseGPT(subset[name], kernels=self.kernels) for name in subset}
+                for attr in ("whole_matrix_sweep", "literal_update"):     # an owner's choice, on ITS objects only
+                    if hasattr(self.owner, attr):
+                        for w_ in wrapped.values():
+                            setattr(w_, attr, bool(getattr(self.owner, attr)))
             else:
                 wrapped = {name: WrappedGPT(subset[name], kernels=self.kernels) for name in subset}
             handles = [
@@ -797,11 +801,30 @@ class _BlockwiseWanda:
                 with PhaseTimer.span("sparsegpt.factor (all Linears of a block, one at a time: csrc/cholesky.hip)"):
                     SparseGPT.factor_all([wrapped[n] for n in subset if n not in twins], percdamp=0.01)
             block_items = []
+            # twin sets swept side by side (`SparseGPT.sweep_group`) where the owner asks for it: the
+            # first Linear of a set -> the set; every Hessian of the block is complete by now, so
+            # the order of the sweeps inside a block is free (sparsegpt_pruner.py:382-396)
+            twin_sets = {}
+            if sparsegpt and twins and getattr(self.owner, "sparsegpt_group_twins", False):
+                for a, b in twins.items():
+                    twin_sets.setdefault(b, [b]).append(a)
             for name in subset:
                 assert wrapped[name].nsamples == sum(x.shape[0] for x in inps) * count_factor
                 weight = subset[name].weight.data
                 ratio = sparsity_ratio[f"{module_to_process}.{i}.{name}.weight"]
-                if sparsegpt:           # sparsegpt_pruner.py:394 / :650
+                if twins.get(name) in twin_sets:
+                    continue            # swept with its set, at the set's first Linear
+                if name in twin_sets:
+                    members = twin_sets[name]
+                    ratios = [sparsity_ratio[f"{module_to_process}.{i}.{m}.weight"] for m in members]
+                    if SparseGPT.sweep_group([wrapped[m] for m in members], ratios, prune_n=self.owner.prune_n,
+                                             prune_m=self.owner.prune_m, blocksize=128, percdamp=0.01):
+                        stats_ = self.owner.stage_stats
+                        stats_["sparsegpt_group_calls"] = stats_.get("sparsegpt_group_calls", 0) + 1
+                        stats_.setdefault("sparsegpt_group_members", []).append(len(members))
+                    for m in members:
+                        wrapped[m].H = None
+                elif sparsegpt:         # sparsegpt_pruner.py:394 / :650
                     wrapped[name].fasterprune(ratio, prune_n=self.owner.prune_n,
                                               prune_m=self.owner.prune_m, percdamp=0.01,
                                               blocksize=128,

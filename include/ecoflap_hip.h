@@ -436,6 +436,36 @@ int ecoflap_sparsegpt_matrix(void* w, int dtype, int64_t rows, int64_t cols, con
                              const int64_t* ranks_host, int prune_n, int prune_m, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* The whole column sweep of up to 8 Linears that share one Hinv (the same input, hence the same
+ * Hessian: q / k / v, gate / up of a decoder block) from one host call,
+ * replaces SparseGPT.fasterprune after the factorisation, once per member
+ *     CoOp/trainers/pruners/sparsegpt_pruner.py:176-189, :261-302, :307
+ * (the lines of ecoflap_sparsegpt_matrix).  The members share cols, dtype, Hinv / ldh, dead,
+ * blocksize and prune_n / prune_m; each has its own contiguous w[rows, cols] (pruned in place), its
+ * own rows and its own HOST ranks (as ranks_host above; may be NULL under n:m).
+ * Contract: every member ends with exactly the bits ecoflap_sparsegpt_matrix gives it when called
+ * alone with the same arguments; a group of one is that call.  Per column block the launches are
+ * those of ONE matrix whatever n_items is: one clear of the selection states, three histogram
+ * passes (a member dimension in the grid; a state, a rank and a histogram per member), one sweep
+ * and one trailing update over the stacked rows.  Every member is checked as the single entry
+ * checks it (ECOFLAP_ESIZE for 0 or more than ECOFLAP_SGPT_MAX_GROUP members) before anything is
+ * queued; then launches only.  workspace: >= ecoflap_sparsegpt_matrix_group_workspace_bytes (the
+ * stacked fp32 copy with each member on a 4-row boundary, Err, one state per member), 16-byte
+ * aligned.  launches_out (optional): HOST int64[5], what this call queued — state clears,
+ * histogram launches, sweeps, trailing updates, widen + narrow launches. */
+#define ECOFLAP_SGPT_MAX_GROUP 8
+typedef struct ecoflap_sgpt_group_item {
+    void* w;                     /* [rows, cols] of the group's dtype, contiguous, pruned in place */
+    int64_t rows;
+    const int64_t* ranks_host;   /* HOST int64[ceil(cols / blocksize)]; NULL allowed under n:m */
+} ecoflap_sgpt_group_item;
+size_t ecoflap_sparsegpt_matrix_group_workspace_bytes(const ecoflap_sgpt_group_item* items, int n_items,
+                                                      int64_t cols);
+int ecoflap_sparsegpt_matrix_group(const ecoflap_sgpt_group_item* items, int n_items, int dtype,
+                                   int64_t cols, const float* Hinv, int64_t ldh, const uint8_t* dead,
+                                   int blocksize, int prune_n, int prune_m, void* workspace,
+                                   size_t workspace_bytes, void* stream, int64_t* launches_out);
+
 /* SparseGPT Hessian accumulation, the path's one GEMM-shaped
  * contraction, on the matrix cores:
  * replaces SparseGPT.add_batch   LAVIS/lavis/compression/pruners/sparsegpt_pruner.py:71-82
