@@ -4,7 +4,7 @@ LDS / VMEM per block, with the branch targets, so that loop bodies can be told a
 by their trip counts (profiles/r04_secondary/k7_rows_phases.md).
 
     hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -Iinclude -Iecoflap_amd/csrc \\
-        -S --cuda-device-only -o /tmp/wanda.s ecoflap_amd/csrc/wanda.hip
+        -S --cuda-device-only -o /tmp/wanda.s ecoflap_amd/csrc/wanda_rows_bf16.hip
     python3 tools/isa_phases.py /tmp/wanda.s _Z22wanda_rows_wave_kernelILi2ELi4EEv9RowsGroup
 """
 import re
