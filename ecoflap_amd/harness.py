@@ -30,7 +30,11 @@ def build_parser():
     p.add_argument("--shape", default="blip2", choices=["blip2", "t5", "vit", "clip", "llama"],
                    help="blip2: EVA-ViT-g + Q-Former + FlanT5-XL; t5: FlanT5-XL; vit: ViT-B/16 CLIP shape; "
                         "clip: OpenAI-CLIP ViT-B/16, both towers (CoOp's zero-shot trainer); "
-                        "llama: LLaMA-7B decoder in fp16 at 2048 tokens (LLaMA/main.py)")
+                        "llama: LLaMA-7B decoder in fp16 at 2048 tokens (LLaMA/main.py; --llama_model)")
+    p.add_argument("--llama_model", default="7b", choices=["7b", "3-8b", "2-70b"],
+                   help="--shape llama: LLaMA-7B, Llama-3-8B or Llama-2-70B (the last two: grouped-query "
+                        "attention, 8 key / value heads); with --toy a choice other than 7b builds the toy "
+                        "with 2 query heads on 1 key / value head")
     p.add_argument("--toy", action="store_true", help="CPU-sized shapes of the same families")
     p.add_argument("--device", default="cuda")
     # the reference's flags (names, types, defaults)
@@ -100,10 +104,13 @@ def build_model_and_loader(args, device):
         from .shapes.unstaged import hide_stage_plan
         hide_stage_plan(Blip2T5, _T5, EVACLIP)
     if args.shape == "llama":
-        from .shapes.llama import llama_7b, llama_batches, llama_tiny
+        from .shapes.llama import llama2_70b, llama3_8b, llama_7b, llama_batches, llama_tiny
         with torch.device(device):
-            model = (llama_tiny(dtype=torch.float32 if device.type == "cpu" else torch.float16)
-                     if args.toy else llama_7b())
+            if args.toy:
+                model = llama_tiny(dtype=torch.float32 if device.type == "cpu" else torch.float16,
+                                   heads=2, kv_heads=None if args.llama_model == "7b" else 1)
+            else:
+                model = {"7b": llama_7b, "3-8b": llama3_8b, "2-70b": llama2_70b}[args.llama_model]()
         loader = llama_batches(args.num_data, bs, model.seqlen, model.config.vocab_size, seed=args.seed,
                                device=device)
     elif args.shape == "blip2":

@@ -45,6 +45,8 @@ def _get():
                                                     i64, i64, i64, i64, f32, ci, vp]
         lib.ecoflap_causal_attention.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64,
                                                  f32, ci, vp]
+        lib.ecoflap_causal_attention_gqa.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64,
+                                                     i64, i64, i64, i64, f32, ci, ci, vp]
         lib.ecoflap_causal_lm_loss.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64, i64, ci, ci, vp]
         lib.ecoflap_multi_copy.argtypes = [vp, ci, vp]
         lib.ecoflap_multi_compare.argtypes = [vp, ci, vp, vp]
@@ -257,25 +259,38 @@ def mha_attention(qkv, heads, scale, causal=False, seq_first=True):
     return out
 
 
-def causal_attention(q, k, v, heads, scale, rope=None):
+def causal_attention(q, k, v, heads, scale, rope=None, kv_heads=None, heads_per_workgroup=0):
     """softmax(rot(q) rot(k)^T * scale + causal mask) v per (sample, head) of a LLaMA decoder block,
     straight from the outputs of the q / k / v projections — three [B, T, heads * 128] fp16 tensors
     with the same strides (three tensors, or three slices of one buffer: read in place) — into the
     merged heads [B, T, heads * 128], contiguous (`ecoflap_causal_attention`,
     csrc/causal_attention.hip).  rope: None (no rotation) or (cos, sin), fp32 [T, 64] on the
     device: the rotate_half rotary embedding of positions 0 .. T - 1, applied inside the kernel.
+    kv_heads (grouped-query attention; None or `heads`: the call above): k and v are
+    [B, T, kv_heads * 128] with equal strides between the two, query head h reads KV head
+    h // (heads // kv_heads) (transformers' `repeat_kv` order) and nothing is expanded in memory
+    (`ecoflap_causal_attention_gqa`; heads_per_workgroup as documented there, 0: the build's choice).
     -> tensor or None (caller runs the torch op chain): the refusal rules of `mha_attention`, and
     the shapes the kernel does not serve (head width != 128, more than 4096 tokens)."""
     import os
     if (torch.is_grad_enabled() or q.device.type != "cuda" or q.dtype != torch.float16 or q.dim() != 3
             or os.environ.get("ECOFLAP_NO_FUSED_ATTENTION")):
         return None
-    for t in (q, k, v):
-        if (t.dtype != q.dtype or t.device != q.device or t.shape != q.shape or t.stride() != q.stride()
-                or t.stride(2) != 1):
+    gqa = kv_heads is not None and kv_heads != heads
+    if q.stride(2) != 1:
+        return None
+    for t in (k, v):
+        if t.dtype != q.dtype or t.device != q.device or t.dim() != 3 or t.stride(2) != 1:
+            return None
+        if gqa:
+            if t.shape != k.shape or t.stride() != k.stride() or t.shape[:2] != q.shape[:2]:
+                return None
+        elif t.shape != q.shape or t.stride() != q.stride():
             return None
     B, T, C = q.shape
     if heads < 1 or C != heads * 128 or not (1 <= T <= 4096) or B < 1 or not (0.0 < float(scale) < float("inf")):
+        return None
+    if gqa and (kv_heads < 1 or heads % kv_heads != 0 or k.shape[2] != kv_heads * 128):
         return None
     cos = sin = None
     if rope is not None:
@@ -285,15 +300,23 @@ def causal_attention(q, k, v, heads, scale, rope=None):
                     or not t.is_contiguous()):
                 return None
     out = torch.empty(B, T, C, dtype=q.dtype, device=q.device)
-    rc = _get().ecoflap_causal_attention(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
-        None if cos is None else cos.data_ptr(), None if sin is None else sin.data_ptr(),
-        B, T, heads, 128, q.stride(1), q.stride(0), out.stride(1), out.stride(0), float(scale),
-        _hip.DTYPE_CODE[q.dtype], _stream())
+    cos_p, sin_p = (None if cos is None else cos.data_ptr()), (None if sin is None else sin.data_ptr())
+    if gqa:
+        name = "ecoflap_causal_attention_gqa"
+        rc = _get().ecoflap_causal_attention_gqa(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), cos_p, sin_p, B, T, heads, kv_heads, 128,
+            q.stride(1), q.stride(0), k.stride(1), k.stride(0), out.stride(1), out.stride(0), float(scale),
+            int(heads_per_workgroup), _hip.DTYPE_CODE[q.dtype], _stream())
+    else:
+        name = "ecoflap_causal_attention"
+        rc = _get().ecoflap_causal_attention(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), cos_p, sin_p,
+            B, T, heads, 128, q.stride(1), q.stride(0), out.stride(1), out.stride(0), float(scale),
+            _hip.DTYPE_CODE[q.dtype], _stream())
     if rc in (-3, -5):      # ECOFLAP_ESIZE / ECOFLAP_EALIGN: a view the kernel cannot address in place
         return None
     if rc != 0:
-        raise _hip.EcoflapHipError(f"ecoflap_causal_attention failed ({rc})")
+        raise _hip.EcoflapHipError(f"{name} failed ({rc})")
     return out
 
 

@@ -1,6 +1,7 @@
 """LLaMA decoder shape (plumbing): random-init, with the parameter names, shapes and
 `named_parameters()` order of transformers' `LlamaForCausalLM` (`tie_word_embeddings=False`, no
-biases, `kv_heads == heads`) — the model the reference's `LLaMA/main.py` loads through
+biases; `num_key_value_heads` below `num_attention_heads` gives grouped-query attention: narrower
+`k_proj` / `v_proj`, query head h reading KV head h // (heads // kv_heads)) — the model the reference's `LLaMA/main.py` loads through
 `AutoModelForCausalLM` in fp16 with `seqlen = 2048`:
 
     model.embed_tokens
@@ -17,10 +18,13 @@ biases, `kv_heads == heads`) — the model the reference's `LLaMA/main.py` loads
 On the CPU, with autograd, or in a dtype other than fp16 a block runs transformers' eager op chain
 (tests/test_llama_shape_golden.py pins it to transformers' own logits bit for bit): RMSNorm with
 fp32 statistics and `weight * x.to(dtype)`, `q * cos + rotate_half(q) * sin`, `matmul * scale +
-mask`, `softmax(dtype=float32).to(dtype)`, `matmul`.  On the GPU under `no_grad` in fp16 a block
+mask`, `softmax(dtype=float32).to(dtype)`, `matmul`; with grouped-query attention k is rotated at
+`kv_heads` heads and k / v then go through transformers' `repeat_kv` (`expand` + `reshape`;
+tests/test_llama_gqa_shape_golden.py).  On the GPU under `no_grad` in fp16 a block
 runs `fused.t5_rmsnorm` (LLaMA's RMSNorm is T5's formula), the projections through `fused.linear`,
 `fused.causal_attention` with the rotary table (csrc/causal_attention.hip: rotation, mask, online
-softmax and both products in one kernel, the projections' outputs read in place), `o_proj`,
+softmax and both products in one kernel, the projections' outputs read in place; with `kv_heads`
+below `heads` its grouped-query entry, which reads the narrow k / v in place: no `repeat_kv` copy), `o_proj`,
 `fused.t5_add_rmsnorm` for residual + post-attention norm, `fused.silu_mul`, `down_proj` and the
 last residual.  Every `None` from a fused op falls back to the torch op at that site alone; the
 kernel serves head width 128 and up to 4096 tokens.  There, too, the loss comes from
@@ -32,7 +36,10 @@ norm, lm_head, loss) for `PrefixCachedLoss`; `forward` is their composition.  Ca
 are `{"input_ids": LongTensor [B, T]}` and the labels are the ids themselves (`llama_batches`,
 `pruners/losses.py::loss_causal_lm`).
 
-Not here: grouped-query attention, bf16 attention, a KV cache, a tokenizer, datasets, perplexity
+`llama_7b`, `llama3_8b`, `llama2_70b` and `mistral_7b` build the true shapes (under
+`torch.device("meta")` without the memory); `llama_tiny` a toy.
+
+Not here: Mistral's sliding window, bf16 attention, a KV cache, a tokenizer, datasets, perplexity
 evaluation."""
 from types import SimpleNamespace
 
@@ -89,23 +96,31 @@ class LlamaAttention(nn.Module):
         super().__init__()
         self.num_heads, self.head_dim = cfg.num_attention_heads, cfg.head_dim
         self.scaling = self.head_dim ** -0.5
-        inner = self.num_heads * self.head_dim
+        self.num_kv_heads = cfg.num_key_value_heads
+        if self.num_kv_heads < 1 or self.num_heads % self.num_kv_heads != 0:
+            raise ValueError(f"{self.num_heads} heads cannot share {self.num_kv_heads} key / value heads")
+        inner, kv_inner = self.num_heads * self.head_dim, self.num_kv_heads * self.head_dim
         self.q_proj = nn.Linear(cfg.hidden_size, inner, bias=False)
-        self.k_proj = nn.Linear(cfg.hidden_size, inner, bias=False)
-        self.v_proj = nn.Linear(cfg.hidden_size, inner, bias=False)
+        self.k_proj = nn.Linear(cfg.hidden_size, kv_inner, bias=False)
+        self.v_proj = nn.Linear(cfg.hidden_size, kv_inner, bias=False)
         self.o_proj = nn.Linear(inner, cfg.hidden_size, bias=False)
         self.__dict__["_rope"] = rope           # the model's table cache (not a submodule)
 
     def torch_attention(self, q, k, v):
-        """transformers' eager chain on the projections' outputs [B, T, H * hd] -> [B, T, H * hd]."""
+        """transformers' eager chain on the projections' outputs (q [B, T, H * hd], k / v
+        [B, T, KVH * hd]) -> [B, T, H * hd]."""
         B, T, _ = q.shape
-        shape = (B, T, self.num_heads, self.head_dim)
-        q, k, v = (t.view(shape).transpose(1, 2) for t in (q, k, v))
+        q = q.view(B, T, self.num_heads, self.head_dim).transpose(1, 2)
+        k, v = (t.view(B, T, self.num_kv_heads, self.head_dim).transpose(1, 2) for t in (k, v))
         cos, sin = self._rope(T, q.device)
         cos = torch.cat((cos, cos), dim=-1).to(q.dtype)[None, None]
         sin = torch.cat((sin, sin), dim=-1).to(q.dtype)[None, None]
         q = (q * cos) + (rotate_half(q) * sin)
         k = (k * cos) + (rotate_half(k) * sin)
+        groups = self.num_heads // self.num_kv_heads
+        if groups > 1:                          # transformers' repeat_kv
+            k, v = (t[:, :, None, :, :].expand(B, self.num_kv_heads, groups, T, self.head_dim)
+                    .reshape(B, self.num_heads, T, self.head_dim) for t in (k, v))
         w = torch.matmul(q, k.transpose(2, 3)) * self.scaling
         mask = torch.full((T, T), torch.finfo(q.dtype).min, dtype=q.dtype, device=q.device).triu_(1)
         w = w + mask[None, None]
@@ -117,7 +132,8 @@ class LlamaAttention(nn.Module):
         y = None
         if self.head_dim == 128 and x.dim() == 3:
             y = fused.causal_attention(q, k, v, self.num_heads, self.scaling,
-                                       rope=self._rope(x.shape[1], x.device) if x.is_cuda else None)
+                                       rope=self._rope(x.shape[1], x.device) if x.is_cuda else None,
+                                       kv_heads=self.num_kv_heads)
         if y is None:
             y = self.torch_attention(q, k, v)
         return _linear(self.o_proj, y)
@@ -255,8 +271,9 @@ def llama_batches(n, batch_size, seqlen, vocab, seed=0, device=None):
 
 
 def llama_config(hidden_size, heads, intermediate_size, layers, vocab_size, head_dim=None,
-                 rms_norm_eps=1e-6, rope_theta=10000.0):
-    return SimpleNamespace(hidden_size=hidden_size, num_attention_heads=heads, num_key_value_heads=heads,
+                 rms_norm_eps=1e-6, rope_theta=10000.0, kv_heads=None):
+    return SimpleNamespace(hidden_size=hidden_size, num_attention_heads=heads,
+                           num_key_value_heads=heads if kv_heads is None else kv_heads,
                            head_dim=head_dim or hidden_size // heads, intermediate_size=intermediate_size,
                            num_hidden_layers=layers, vocab_size=vocab_size, rms_norm_eps=rms_norm_eps,
                            rope_theta=rope_theta, initializer_range=0.02, use_cache=False,
@@ -275,9 +292,29 @@ def llama_7b(dtype=torch.float16):
     return _build(llama_config(4096, 32, 11008, 32, 32000), dtype, 2048)
 
 
+def llama3_8b(dtype=torch.float16):
+    """Llama-3-8B: 32 layers, 4096 wide, 32 query heads of 128 on 8 key / value heads, MLP 14336,
+    vocabulary 128256, eps 1e-5, theta 500000, fp16."""
+    return _build(llama_config(4096, 32, 14336, 32, 128256, rms_norm_eps=1e-5, rope_theta=500000.0, kv_heads=8),
+                  dtype, 2048)
+
+
+def llama2_70b(dtype=torch.float16):
+    """Llama-2-70B: 80 layers, 8192 wide, 64 query heads of 128 on 8 key / value heads, MLP 28672,
+    vocabulary 32000, eps 1e-5, theta 10000, fp16."""
+    return _build(llama_config(8192, 64, 28672, 80, 32000, rms_norm_eps=1e-5, kv_heads=8), dtype, 2048)
+
+
+def mistral_7b(dtype=torch.float16):
+    """Mistral-7B's shape: 32 layers, 4096 wide, 32 query heads of 128 on 8 key / value heads, MLP
+    14336, vocabulary 32000, eps 1e-5, theta 10000, fp16.  Its sliding window is not modelled: within
+    4096 tokens, the window of v0.1, full causal attention is the same function."""
+    return _build(llama_config(4096, 32, 14336, 32, 32000, rms_norm_eps=1e-5, kv_heads=8), dtype, 2048)
+
+
 def llama_tiny(hidden_size=64, heads=2, head_dim=128, intermediate_size=176, layers=2, vocab_size=96,
-               dtype=torch.float32, seqlen=128):
+               dtype=torch.float32, seqlen=128, kv_heads=None):
     """A toy decoder for tests; head width 128 by default, the width the fused attention serves."""
-    return _build(llama_config(hidden_size, heads, intermediate_size, layers, vocab_size, head_dim=head_dim),
-                  dtype, seqlen)
+    return _build(llama_config(hidden_size, heads, intermediate_size, layers, vocab_size, head_dim=head_dim,
+                               kv_heads=kv_heads), dtype, seqlen)
 

@@ -134,7 +134,9 @@ int ecoflap_mha_attention_colsq(const void* qkv, void* out, float* sq, void* wor
  * with token n's row of rope_cos / rope_sin, [tokens, 64] fp32 on the device (positions 0 ..
  * tokens - 1, no KV cache; rope_theta and scaling variants are the caller's); multiplied in fp32,
  * rotated q and k rounded once to f16, no rotated copy in memory.  Both table pointers NULL: no
- * rotation; one alone: ECOFLAP_ENULL.  Grouped-query attention (kv_heads != heads) is not served.
+ * rotation; one alone: ECOFLAP_ENULL.  Grouped-query attention (kv_heads != heads) is served by
+ * ecoflap_causal_attention_gqa below; this entry is that one with kv_heads = heads, one head per
+ * workgroup and q's strides for k / v.
  * F16 only (else ECOFLAP_EDTYPE); head_dim == 128, 1 <= tokens <= 4096, batch, heads > 0, batch *
  * heads * ceil(tokens / 32) < 2^31, finite scale > 0, token strides at least a row, batch strides
  * >= 0 (else ECOFLAP_ESIZE); pointers 16-byte aligned and every stride a multiple of 8 elements
@@ -149,6 +151,36 @@ int ecoflap_causal_attention(const void* q, const void* k, const void* v, void* 
                              int64_t qkv_token_stride, int64_t qkv_batch_stride,
                              int64_t out_token_stride, int64_t out_batch_stride, float scale,
                              int dtype, void* stream);
+
+/* ecoflap_causal_attention with grouped-query attention (Llama-2-70B, Llama-3, Mistral: fewer key /
+ * value heads than query heads).  A q / out row holds [heads, 128] as above; a k / v row holds
+ * [kv_heads, 128] and starts at ptr + b * kv_batch_stride + n * kv_token_stride (strides of their
+ * own: the k / v projections are narrower tensors, or slices of one fused buffer).  Query head h
+ * reads KV head h / (heads / kv_heads): transformers' repeat_kv order.  No expanded copy of K / V
+ * exists anywhere.
+ * heads_per_workgroup (P), with G = heads / kv_heads: one of 1, 2, 4, 8 and a divisor of G; 0 means
+ * the build's choice, ecoflap_causal_attention_gqa_default_p(G): 1 for every G, by measurement
+ * (profiles/r17_llama_gqa: no larger P was faster beyond the run-to-run spread).  A workgroup of 8 waves serves P
+ * query heads of one KV group times 8 / P query tiles of 32 (256 / P consecutive queries): a K / V
+ * block is fetched, rotated and staged in LDS once for P heads.  P changes the schedule only: the
+ * output of every (sample, head, 32-query tile) is bit for bit what ecoflap_causal_attention writes
+ * for that head on K / V expanded to `heads` heads in memory, for every valid P.
+ * Everything else is ecoflap_causal_attention's contract (F16 only, head_dim == 128, 1 <= tokens <=
+ * 4096, both rope pointers or neither, 16-byte pointers, every stride a multiple of 8 elements, no
+ * atomics, batch invariant bit for bit) and its error codes in its order; in addition ECOFLAP_ESIZE
+ * for kv_heads < 1, heads % kv_heads != 0, an invalid heads_per_workgroup and a kv token stride
+ * below kv_heads * 128 (the grid is at most batch * heads * ceil(tokens / 32) < 2^31 workgroups).
+ * Nothing is launched on an error. */
+int ecoflap_causal_attention_gqa(const void* q, const void* k, const void* v, void* out,
+                                 const float* rope_cos, const float* rope_sin, int64_t batch,
+                                 int64_t tokens, int64_t heads, int64_t kv_heads, int64_t head_dim,
+                                 int64_t q_token_stride, int64_t q_batch_stride,
+                                 int64_t kv_token_stride, int64_t kv_batch_stride,
+                                 int64_t out_token_stride, int64_t out_batch_stride, float scale,
+                                 int heads_per_workgroup, int dtype, void* stream);
+
+/* What heads_per_workgroup == 0 stands for at group size G = heads / kv_heads (0 for G < 1). */
+int ecoflap_causal_attention_gqa_default_p(int64_t group);
 
 /* The causal language-model loss of a decoder, from the 16-bit logits its lm_head wrote
  * (transformers' ForCausalLMLoss: labels padded by one ignore_index and shifted, flat fp32 cross
